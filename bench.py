@@ -13,7 +13,8 @@ cycle end: triangular solve, x update, explicit residual) of
 timed region is a fixed number of cycles and the expected ConvergenceError is caught).
 Inputs (CSR matrix, b) are resident in HBM before the timed region starts.
 
-value = K*100 iterations / wall time (max over ranks, barrier + device sync on both sides).
+value = K*100 iterations / wall time (max over ranks, barrier + device sync on both sides); ms_per_step = the wall
+time of one timed cycle.  A plain run sets up, warms up, times the K cycles and prints the line - nothing else.
 For N > 1 the matrix rows and all vectors are sharded in contiguous slabs, one process per GPU.  ``python bench.py
 --gpus N`` with no RANK / WORLD_SIZE in the environment starts the N rank processes ITSELF (`_launch`: LOCAL_RANK = i,
 KRYPY_AMD_DEVICE = i, a free MASTER_PORT on 127.0.0.1; fewer than N visible devices is an error, never a silent N = 1);
@@ -22,11 +23,18 @@ exchange + dot-product all-reduces go through RCCL inside libkrylov_hip.so; the 
 ranks, and the timing barrier / max-over-ranks run, over krypy_amd.dist.TcpRendezvous (plain sockets: no
 PyTorch on the host side).  Total work is fixed -> "scaling": "strong".
 
-Extra objects on the JSON line:
+``--full`` measures, after the timed cycles, what the headline figure does not need, and adds it to the line:
   roofline     the dominant kernel (Gram-Schmidt link / panel kernels), timed live with HIP
                events on the library's stream; algorithmic bytes per SURVEY.md 8(d).
   cpu_baseline the CPU oracle (NumPy/SciPy restatement of the reference) timed on a bounded
                sample of the same workload on the host cores (rank 0, N = 1 only).
+  other_modes, basis_orthogonality_fro, secondary (config 3 on the same matrix), and on N > 1 ranks
+               sharded_diagnostics (one more untimed cycle).
+Without it those keys are null or absent.  `--config 3 / 4 / 5` are legs of their own and measure as they always did.
+
+``--dump-outputs DIR`` (config 2) writes what the timed run returns to its caller after its last cycle, float64:
+  DIR/x.npy        the iterate x, at 2^20 rows drawn once with numpy.random.default_rng(2024) (sorted; all rows if N is smaller)
+  DIR/resnorms.npy the relative residual norms of the timed cycles (K*100 + 1 values)
 """
 import argparse
 import json
@@ -136,8 +144,14 @@ def parse_args():
                          "reference's sequential order, register-resident chain kernel) and cgs on "
                          "several GPUs (panel classical GS: one all-reduce per step instead of k+1). "
                          "Also: mgs | dmgs | cgs | cgs2.  All pass the 1e-10 parity tests.")
+    ap.add_argument("--full", action="store_true",
+                    help="config 2: after the timed region also measure the roofline, the CPU baseline, the other Gram-Schmidt "
+                         "variants, the basis orthogonality, config 3 on the same matrix and (N > 1) the per-rank diagnostics")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="config 2: write the timed run's outputs after its last cycle to DIR/*.npy (float64): x at a seeded "
+                         "sample of 2^20 rows, resnorms")
     ap.add_argument("--other-modes", default="cgs,cgs2",
-                    help="comma list of further variants measured AFTER the timed region (N=1 only)")
+                    help="with --full: comma list of further variants measured AFTER the timed region (N=1 only)")
     ap.add_argument("--force-sharded", action="store_true",
                     help="testing: take the multi-GPU code path (gloo init, RCCL communicator, "
                          "ShardedCSROperator, all-reduced reductions) even with one rank")
@@ -165,6 +179,8 @@ def parse_args():
     args = ap.parse_args()
     if args.loop_halo and not (args.force_sharded and args.gpus == 1):
         ap.error("--loop-halo: with --force-sharded on one rank (--gpus 1)")
+    if args.dump_outputs and args.config != 2:
+        ap.error("--dump-outputs: config 2 only")
     return args
 
 
@@ -489,6 +505,26 @@ def _rank_table(dist, value):
     return [struct.unpack("<d", x)[0] for x in dist.allgather_bytes(struct.pack("<d", float(value)))]
 
 
+DUMP_ROWS = 1 << 20       # 8 MB of the iterate: a fixed sample, the same rows in every run of the same size
+
+
+def _dump_outputs(path, sol, n_global, row0, dist, rank):
+    """--dump-outputs: the iterate at a seeded sample of rows and the residual history of the timed run, float64, as
+    DIR/x.npy and DIR/resnorms.npy (rank 0 writes; on N > 1 ranks each rank fills the sampled rows of its slab)."""
+    x = np.asarray(sol.xk, dtype=np.float64).reshape(-1)
+    rows = np.arange(n_global) if n_global <= DUMP_ROWS else \
+        np.sort(np.random.default_rng(2024).choice(n_global, size=DUMP_ROWS, replace=False))
+    mine = (rows >= row0) & (rows < row0 + x.size)
+    xs = np.zeros(rows.size)
+    xs[mine] = x[rows[mine] - row0]
+    if dist is not None:
+        xs = np.sum([np.frombuffer(p, dtype=np.float64) for p in dist.allgather_bytes(xs.tobytes())], axis=0)
+    if rank == 0:
+        os.makedirs(path, exist_ok=True)
+        np.save(os.path.join(path, "x.npy"), xs)
+        np.save(os.path.join(path, "resnorms.npy"), np.asarray(sol.resnorms, dtype=np.float64))
+
+
 def _spmv_us(ctx, opnd, n, reps=20):
     """this rank's sharded (or plain) SpMV, microseconds per product by HIP events on the library's stream"""
     X, Y = ctx.alloc(n, 1), ctx.alloc(n, 1)
@@ -671,10 +707,13 @@ def _run():
     n_iters = len(sol.resnorms) - 1
     assert n_iters == args.steps * m, (n_iters, args.steps, m)
     its = n_iters / dt
+    if args.dump_outputs:
+        row0 = cuts[rank] * nx if sharded and not args.loop_halo else 0
+        _dump_outputs(args.dump_outputs, sol, N, row0, dist, rank)
 
     # ---- what a first run on real links needs to be read: per-rank SpMV time, sums per iteration and what carried them ----
     shard_diag = None
-    if sharded:
+    if sharded and args.full:
         keys = ("n_allreduce", "n_xr", "n_halo_exchange", "n_halo_xh", "n_chain_blk2", "n_chain_xr", "n_lowsync")
         try:
             c0 = dict((k, ctx.get(k)) for k in keys) if hasattr(ctx, "get") else {}
@@ -702,19 +741,21 @@ def _run():
         G = ctx.gemm_tn(Vb, 0, m + 1, Vb, 0, m + 1)
         return float(np.linalg.norm(G - np.eye(m + 1)))
 
-    orth = {}
-    try:
-        orth[ortho] = basis_orthogonality(ortho)
-        if not sharded:          # one GPU: both the reference order and the panel form the N > 1 runs default to
-            for mode in ("mgs", "cgs"):
-                if mode not in orth:
-                    orth[mode] = basis_orthogonality(mode)
-    except Exception as exc:
-        orth["error"] = repr(exc)
+    orth = None
+    if args.full:
+        orth = {}
+        try:
+            orth[ortho] = basis_orthogonality(ortho)
+            if not sharded:          # one GPU: both the reference order and the panel form the N > 1 runs default to
+                for mode in ("mgs", "cgs"):
+                    if mode not in orth:
+                        orth[mode] = basis_orthogonality(mode)
+        except Exception as exc:
+            orth["error"] = repr(exc)
 
     # ---- the other Gram-Schmidt variants on the same inputs (outside the timed region) ----
     others = {}
-    if not sharded and args.other_modes:
+    if args.full and not sharded and args.other_modes:
         for mode in [t for t in args.other_modes.split(",") if t and t != ortho and t != "none"]:
             barrier()
             t1 = time.perf_counter()
@@ -730,7 +771,7 @@ def _run():
     # step like 'cgs', the reference's recurrence in exact arithmetic; all-reduces per Arnoldi step are counted
     # (on one rank in forced mode by default; on a real N-rank run only with KRYPY_AMD_BENCH_SHARDED_EXTRAS=1 - the one-reduction form
     # has run through a 1-rank communicator only, and an untimed extra must not be able to cost the run its line)
-    if (sharded and args.other_modes and hasattr(ctx, "get")
+    if (args.full and sharded and args.other_modes and hasattr(ctx, "get")
             and (world == 1 or os.environ.get("KRYPY_AMD_BENCH_SHARDED_EXTRAS", "0") == "1")):
         for mode in [t for t in ("cgs", "mgs") if t != ortho]:
             barrier()
@@ -750,7 +791,7 @@ def _run():
 
     # the reference-order solver on a GENERAL CSR operator (the CSR-stream SpMV kernel + the chain kernel: what a matrix
     # that is not a stencil gets), and with the banded SpMV as a launch of its own (no operator in the chain's prologue)
-    if not sharded and args.other_modes and ortho == "mgs" and hasattr(ctx, "set"):
+    if args.full and not sharded and args.other_modes and ortho == "mgs" and hasattr(ctx, "set"):
         for label, key in (("mgs, general CSR SpMV kernel + chain kernel (spmv_dia = 0, as KRYPY_AMD_SPMV_DIA=0)", "spmv_dia"),
                            ("mgs, banded SpMV launch + chain kernel (chain_spmv = 0, as KRYPY_AMD_CHAIN_SPMV=0)", "chain_spmv")):
             barrier()
@@ -769,18 +810,19 @@ def _run():
     nloc = ls.N
     roof = None
     extra = {}
-    try:
-        from krypy_amd import _bench
-        if args.no_roofline:
-            raise RuntimeError("skipped (--no-roofline)")
-        import glob
-        # HBM bytes per launch from PMC passes of this same command (tools/profile.sh + tools/summarize_prof.py;
-        # bench.py cannot collect counters itself): attached only if the file carries the stamp of the kernel
-        # sources that have just been timed, otherwise `traffic` stays null and the byte model is used
-        tfiles = sorted(glob.glob(os.path.join(ROOT, "profiles", "*_traffic.json")))
-        roof, extra = _bench.roofline(ctx, ls, ortho, HBM_PEAK_GBS, traffic_files=tfiles, m=m)
-    except Exception as exc:   # never lose the headline number to the instrumentation
-        extra = {"roofline_error": repr(exc)}
+    if args.full:
+        try:
+            from krypy_amd import _bench
+            if args.no_roofline:
+                raise RuntimeError("skipped (--no-roofline)")
+            import glob
+            # HBM bytes per launch from PMC passes of this same command (tools/profile.sh + tools/summarize_prof.py;
+            # bench.py cannot collect counters itself): attached only if the file carries the stamp of the kernel
+            # sources that have just been timed, otherwise `traffic` stays null and the byte model is used
+            tfiles = sorted(glob.glob(os.path.join(ROOT, "profiles", "*_traffic.json")))
+            roof, extra = _bench.roofline(ctx, ls, ortho, HBM_PEAK_GBS, traffic_files=tfiles, m=m)
+        except Exception as exc:   # never lose the headline number to the instrumentation
+            extra = {"roofline_error": repr(exc)}
 
     out = {
         "metric": "GMRES iterations/sec + SpMV HBM GB/s, n=10^7 5-pt Laplacian fp64",
@@ -825,7 +867,7 @@ def _run():
     out.update(extra)
     if others:
         out["other_modes"] = others
-    if not sharded and os.environ.get("KRYPY_AMD_BENCH_SECONDARY", "1") != "0" and hasattr(ctx, "get"):
+    if args.full and not sharded and os.environ.get("KRYPY_AMD_BENCH_SECONDARY", "1") != "0" and hasattr(ctx, "get"):
         # one secondary configuration driver-timed in every round: BASELINE.json configs[2], MINRES + Jacobi
         # on this very matrix, 2 x 200 iterations after one warm-up solve (< 2 s); `bench.py --config 3` is the full leg
         try:
@@ -837,7 +879,7 @@ def _run():
                                                                   "`python bench.py --config 3` carries its roofline and CPU baseline"}}
         except Exception as exc:
             out["secondary"] = {"config3_minres_jacobi": {"error": repr(exc)[:300]}}
-    if rank == 0 and not sharded and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not sharded and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline(A_for_ls, b, m, args.cpu_budget_s)
         except Exception as exc:

@@ -120,7 +120,7 @@ SWITCHES = [
     ("KRYPY_AMD_FORCE_MULTI", "0", "test", None,
      "1: run the multi-rank code path (cross-rank sums, halo hook) on a 1-rank communicator"),
     ("KRYPY_AMD_BENCH_SHARDED_EXTRAS", "0", "bench", None,
-     "1: a `bench.py` run on N > 1 ranks also times the other Gram-Schmidt order (`mgs` beside the `cgs` default) and reports its "
+     "1: a `bench.py --full` run on N > 1 ranks also times the other Gram-Schmidt order (`mgs` beside the `cgs` default) and reports its "
      "cross-rank sums per iteration and orthogonality, outside the timed region (on one rank in `--force-sharded` mode it always does)"),
     ("KRYPY_AMD_BENCH_DEVICES", "unset", "bench", None,
      "set by `bench.py`'s own launcher for the rank processes it starts: the number of distinct devices the run uses (`n_gpus` of the line; "
@@ -129,7 +129,7 @@ SWITCHES = [
      "`bench.py --ortho` default (`auto` = `mgs` on 1 GPU; on N ranks one untimed cycle per (form, transport) candidate, the fastest "
      "that ran on every rank is timed)"),
     ("KRYPY_AMD_BENCH_SECONDARY", "1", "bench", None,
-     "0: the default `bench.py` line does not carry `secondary.config3_minres_jacobi` (MINRES + Jacobi on the timed run's matrix, "
+     "0: the `bench.py --full` line does not carry `secondary.config3_minres_jacobi` (MINRES + Jacobi on the timed run's matrix, "
      "2 x 200 iterations after the timed region)"),
     ("KRYPY_AMD_BENCH_XR_TIMEOUT_S", "15", "bench", None,
      "seconds a cross-rank sum over the mailboxes may wait for a peer inside `bench.py`'s timed region before the run goes back to RCCL "

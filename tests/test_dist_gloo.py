@@ -306,7 +306,7 @@ def test_bench_gpus_n_starts_its_own_ranks(world):
     the iterations are the single-process ones."""
     import json
     rc, lines, err = _bench_self_spawn(["--gpus", str(world), "--steps", "2", "--warmup", "1", "--nx", "40", "--ny",
-                                        "36", "--restart", "12", "--no-roofline", "--no-cpu-baseline"])
+                                        "36", "--restart", "12", "--full", "--no-roofline", "--no-cpu-baseline"])
     assert rc == 0, err[-3000:]
     assert len(lines) == 1, lines
     o = json.loads(lines[0])
@@ -325,6 +325,30 @@ def test_bench_gpus_n_starts_its_own_ranks(world):
     assert o["config"]["basis_orthogonality_fro"][chosen] < 1e-10
     diag = o["config"]["sharded_diagnostics"]
     assert len(diag["rows_per_rank"]) == world and sum(diag["rows_per_rank"]) == 40 * 36 and len(diag["spmv_us_per_rank"]) == world
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain `bench.py` line carries the headline and no extra measurement (those are `--full`'s); `--dump-outputs DIR`
+    writes the timed run's iterate and residual history as float64, the same on one rank and on two."""
+    import json
+    argv = ["--steps", "2", "--warmup", "1", "--nx", "40", "--ny", "36", "--restart", "12", "--ortho", "cgs"]
+    dumps = {}
+    for world in (1, 2):
+        d = str(tmp_path / ("w%d" % world))
+        rc, lines, err = _bench_self_spawn(["--gpus", str(world), "--dump-outputs", d] + argv)
+        assert rc == 0 and len(lines) == 1, err[-3000:]
+        o = json.loads(lines[0])
+        assert o["config"]["iterations_timed"] == 24 and abs(o["ms_per_step"] * 2 / 1e3 * o["value"] - 24) < 1e-6
+        assert o["roofline"] is None and o["config"]["basis_orthogonality_fro"] is None
+        assert o["config"]["sharded_diagnostics"] is None
+        assert not {"cpu_baseline", "other_modes", "secondary"} & set(o)
+        dumps[world] = dict((k, np.load(os.path.join(d, k + ".npy"))) for k in ("x", "resnorms"))
+        assert all(a.dtype == np.float64 for a in dumps[world].values())
+        assert dumps[world]["x"].shape == (40 * 36,) and dumps[world]["resnorms"].shape == (25,)
+        assert dumps[world]["resnorms"][-1] == o["config"]["final_relres"]
+    want = _single_process_bench_residual(40, 36, 12, ortho="cgs")
+    assert abs(dumps[1]["resnorms"][-1] - want) <= 1e-9 * want
+    assert np.linalg.norm(dumps[2]["x"] - dumps[1]["x"]) <= 1e-10 * np.linalg.norm(dumps[1]["x"])
 
 
 def test_bench_gpus_n_refuses_when_fewer_devices_are_visible():

@@ -132,7 +132,7 @@ def test_bench_timed_region_fallback_on_the_real_context(hip):
     must not cost the run its line: the mailboxes are detached, the halo goes back to ncclSend / ncclRecv, the panel form over
     ncclAllReduce is timed instead - on the REAL context (the CPU suite runs the same logic on the double) - and the line says
     so; the residual is the one of a plain `--ortho cgs` run over RCCL."""
-    common = ["--force-sharded", "--steps", "2", "--warmup", "1", "--nx", "4000", "--ny", "700", "--restart", "30",
+    common = ["--force-sharded", "--steps", "2", "--warmup", "1", "--nx", "4000", "--ny", "700", "--restart", "30", "--full",
               "--no-cpu-baseline", "--no-roofline", "--other-modes", "none"]
     os.environ["KRYPY_AMD_BENCH_FAULT"] = "1"
     try:

@@ -18,7 +18,7 @@ bench)
   # the headline: kernel trace + PMC passes of the default (reference-order) bench command, then the line itself (the
   # traffic file just written carries the stamp of these sources)
   prof r06_bench_mgs_chain --ortho mgs --other-modes none
-  python bench.py > $EV/profiles/r06_bench.json 2> $EV/r06_bench.err
+  python bench.py --full > $EV/profiles/r06_bench.json 2> $EV/r06_bench.err
   tail -c 300 $EV/profiles/r06_bench.json
   ;;
 legs)

@@ -34,7 +34,7 @@ def main(src, dst):
         try:
             b = json.loads(open(bj).read().strip().splitlines()[-1])
             extra_args = " ".join(sys.argv[3:])
-            lines += ["Command: `rocprofv3 --kernel-trace --stats -- python bench.py --steps %d --warmup %d "
+            lines += ["Command: `rocprofv3 --kernel-trace --stats -- python bench.py --full --steps %d --warmup %d "
                       "--no-cpu-baseline %s` (tools/profile.sh) on one MI355X; workload: %s" % (
                           b["steps"], b["warmup"], extra_args or ("--ortho %s --other-modes none" % b["config"].get("ortho")),
                           b["config"].get("workload", "")),
