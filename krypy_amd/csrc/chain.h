@@ -72,8 +72,10 @@ struct ChainArgs {
     int* donepin;
     int done_tag;
     // fused operator (k_mgs_chain_lds<..., FND > 0>): w = A x computed by the prologue straight into
-    // registers from the diagonal-major copy of a banded operator instead of being loaded
+    // registers from the banded form of the operator instead of being loaded: its diagonal-major copy, or - when dmask is
+    // not null - the presence masks of its row pairs and the values in offs.cst (kernels.h: dia_slot)
     const double* dia;
+    const uint16_t* dmask;
     int64_t dia_ld;
     const double* xk;
     int64_t n_last;    // n - 1
@@ -698,11 +700,11 @@ __device__ __forceinline__ void chain_apply_banded_z(const ChainArgs& a, int64_t
     }
 }
 
-template <int R2, int FND, int RIF = KH_RIF, class Put>
-__device__ __forceinline__ void chain_apply_banded(const ChainArgs& a, int64_t first, Put&& put) {
+template <int R2, int FND, int RIF, bool MASK, class Put>
+__device__ __forceinline__ void chain_apply_banded_form(const ChainArgs& a, int64_t first, Put&& put) {
     // w = A x_k for this lane's rows, exactly as k_spmv_dia computes them (ascending offsets,
     // separate multiply and add, empty slots skipped): the 80 MB of w are never written nor read.
-    // The padding rows behind n hold zeros in every diagonal and come out as w = 0.
+    // The padding rows behind n hold zeros in every diagonal (no bit in their masks) and come out as w = 0.
     const double* __restrict__ xk = a.xk;
     const int64_t last = a.n_last;
     int64_t fb = first;      // passed through an opaque asm every two rows: that is what bounds the
@@ -720,10 +722,11 @@ __device__ __forceinline__ void chain_apply_banded(const ChainArgs& a, int64_t f
         const int64_t row = 2 * i2;
         double2 av[FND];
         double x0[FND], x1[FND];
+        const unsigned m = MASK ? dia_mask_load(a.dmask, i2) : 0u;
 #pragma unroll
         for (int d = 0; d < FND; ++d) {
             const int64_t off = a.offs.off[d];
-            av[d] = ld_nt2(reinterpret_cast<const double2*>(a.dia + (int64_t)d * a.dia_ld) + i2);
+            av[d] = dia_slot<MASK>(a.dia, a.dia_ld, d, i2, m, MASK ? a.offs.cst[d] : 0.0);
             // branch-free (clamped scalar loads of x: L2 hits): control flow in this fully
             // unrolled prologue sends the register allocator into > 1000 spills
             int64_t c0 = row + off, c1 = row + 1 + off;
@@ -742,6 +745,15 @@ __device__ __forceinline__ void chain_apply_banded(const ChainArgs& a, int64_t f
         put(r, s0, s1);         // (row r of w: a register, or - long shapes - this lane's LDS entry)
         if ((r & RIF) == RIF) asm volatile("" : "+v"(fb) : : "memory");   // four rows of loads in flight (with the running index of rounds 1-2: one 1023 it/s, two 1028-1037, four 1018-1030; with the constant distances: two 1087-1089, four 1093-1095 on one box)
     }
+}
+
+// The operator's form is chosen by ONE wave-uniform branch (a kernel argument) around two straight-line copies of the
+// row loop, never inside it: no new kernel symbols, and the unrolled loop itself stays free of control flow.
+template <int R2, int FND, int RIF = KH_RIF, class Put>
+__device__ __forceinline__ void chain_apply_banded(const ChainArgs& a, int64_t first, Put&& put) {
+    static_assert(FND <= KH_DIA_CMAX, "the mask form holds up to KH_DIA_CMAX diagonals");
+    if (a.dmask != nullptr) chain_apply_banded_form<R2, FND, RIF, true>(a, first, put);
+    else chain_apply_banded_form<R2, FND, RIF, false>(a, first, put);
 }
 
 // WL > 0 (with FND > 0 the operator's rows beyond the registers are put into the LDS entries directly: instantiated for
@@ -1617,11 +1629,14 @@ __global__ __launch_bounds__(CH_BS) void k_mgs_chain_pf(ChainArgs a) {
 // the one-column look-ahead of k_mgs_chain_pf leaves exposed (a link took 1.4 - 1.9 us around a 0.84 us sum) is
 // hidden - and the update takes the column from the same registers the dot used: every column is read once.
 // Same accumulators, same row order, same sums as the other chain kernels: the same bits.  B == V only (no
-// preconditioner), real data; ONEX as above, FND > 0: the banded operator in the prologue.
+// preconditioner), real data; ONEX as above, FND > 0: the banded operator in the prologue, DMASK: in its mask form
+// (a template parameter here, not the one-branch choice of chain_apply_banded: with both copies of the prologue beside
+// the register ring this family spilled - 100 / 164 B of scratch per lane at 8 rows, ONEX)
 // ------------------------------------------------------------------------------------------
-template <int R2, int LA, bool MASKED, int FND = 0, bool ONEX = false>
+template <int R2, int LA, bool MASKED, int FND = 0, bool ONEX = false, bool DMASK = false>
 __global__ __launch_bounds__(ONEX ? CH_BS + 64 : CH_BS) void k_mgs_chain_small(ChainArgs a) {
     static_assert(FND == 0 || !MASKED, "the fused operator exists for padded blocks");
+    static_assert(FND > 0 || !DMASK, "the mask form is a form of the fused operator");
     constexpr int NS = LA + 1;
     __shared__ double smd[4 * (CH_BS / 64)];
     __shared__ unsigned smu[2 * CH_GMAX];
@@ -1671,7 +1686,7 @@ __global__ __launch_bounds__(ONEX ? CH_BS + 64 : CH_BS) void k_mgs_chain_small(C
     CH_ISSUE_FENCE();
     double2 w[R2];
     if constexpr (FND > 0) {
-        chain_apply_banded<R2, FND>(a, first, [&](int r, double s0, double s1) { w[r] = make_double2(s0, s1); });
+        chain_apply_banded_form<R2, FND, KH_RIF, DMASK>(a, first, [&](int r, double s0, double s1) { w[r] = make_double2(s0, s1); });
     } else {
         const double2* __restrict__ win2 = reinterpret_cast<const double2*>(a.w_in) + first;
 #pragma unroll

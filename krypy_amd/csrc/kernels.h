@@ -10,6 +10,8 @@
 //  * compiled with -ffp-contract=off: `w - alpha*p` rounds twice exactly like NumPy's
 //    `Av -= alpha * V[:, [j]]`; fused multiply-adds are used only where written as fma().
 #pragma once
+#include <type_traits>
+
 #include "kh_internal.h"
 #include "xr_dev.h"
 
@@ -658,12 +660,38 @@ __global__ __launch_bounds__(BS) void k_spmm_stream(const int32_t* __restrict__ 
 // rows (16-byte value loads); the diagonals are visited in ascending offset = the storage order of
 // a CSR row with sorted columns, separate multiply and add: the same bits as scipy's csr_matvec
 // and as k_spmv_stream.  Same epilogues and the same XCD-aware block order as the CSR kernel.
+//
+// Constant coefficients (every stored value of a diagonal bitwise equal, at most KH_DIA_CMAX diagonals: the Laplacians
+// of configs 2, 3 and 5) have a second form without the value copy: one presence mask per row pair (uint16_t: bit d of
+// the low / high byte = row 2 i2 / 2 i2 + 1 has an entry on diagonal d; 1 B per row instead of 8 nd) and the nd values
+// in DiaOffs::cst.  dia_slot gives the slot values of either form, and since a slot is non-zero exactly where an entry
+// exists, the arithmetic behind it - and its bits - are the same.
 // ------------------------------------------------------------------------------------------
 constexpr int KH_DIA_MAX = 32;
+constexpr int KH_DIA_CMAX = 8;      // diagonals of the mask form: a row's presence bits fit one byte
 struct DiaOffs {
     int nd;
     int off[KH_DIA_MAX];
+    double cst[KH_DIA_CMAX];        // mask form: the value of diagonal d (unused otherwise)
 };
+
+// Slot values of diagonal d at row pair i2 (rows 2 i2, 2 i2 + 1): from the value copy dia[d * ld + 2 i2 ...], or - MASK -
+// from the row pair's presence bits m (loaded once per row pair) and the diagonal's value c: bit ? c : 0.0.  The form is
+// a template parameter: a kernel branches once, wave-uniformly, around two straight-line copies of its row loop.
+template <bool MASK>
+__device__ __forceinline__ double2 dia_slot(const double* __restrict__ dia, int64_t ld, int d, int64_t i2, unsigned m,
+                                            double c) {
+    if constexpr (MASK) {
+        return make_double2(((m >> d) & 1u) ? c : 0.0, ((m >> (d + 8)) & 1u) ? c : 0.0);
+    } else {
+        return ld_nt2(reinterpret_cast<const double2*>(dia + (int64_t)d * ld) + i2);
+    }
+}
+
+// the presence mask of row pair i2 (streamed once, like the value copy)
+__device__ __forceinline__ unsigned dia_mask_load(const uint16_t* __restrict__ mask, int64_t i2) {
+    return (unsigned)__builtin_nontemporal_load(mask + i2);
+}
 
 // Column of a block-row shard on the axis of its own rows: local columns stay, the ghost columns
 // (CSR ids nloc .. nloc+nprev+nnext, krypy_amd/dist.py) are the rows just before / after the slab:
@@ -687,11 +715,35 @@ static __global__ __launch_bounds__(BS) void k_dia_fill(const int32_t* __restric
     }
 }
 
+// The mask form of the same operator: thread i2 writes the mask of row pair i2 - every one of the npair = ld / 2 entries,
+// so the padding rows come out empty (w = 0 there, as with the zeros of the value copy).
+static __global__ __launch_bounds__(BS) void k_dia_mask_fill(const int32_t* __restrict__ indptr,
+                                                      const int32_t* __restrict__ indices, int64_t n_rows,
+                                                      int nprev, DiaOffs o, uint16_t* __restrict__ mask,
+                                                      int64_t npair) {
+    const int64_t i2 = (int64_t)blockIdx.x * BS + threadIdx.x;
+    if (i2 >= npair) return;
+    unsigned m = 0;
+    for (int h = 0; h < 2; ++h) {
+        const int64_t r = 2 * i2 + h;
+        if (r >= n_rows) break;
+        for (int p = indptr[r]; p < indptr[r + 1]; ++p) {
+            const int off = dia_virtual_col(indices[p], (int)n_rows, nprev) - (int)r;
+            int d = 0;
+            while (d < o.nd - 1 && o.off[d] != off) ++d;
+            m |= 1u << (d + 8 * h);
+        }
+    }
+    mask[i2] = (uint16_t)m;
+}
+
 // XH (with HALO): the halo travels through IPC-mapped granules (xr_dev.h) inside THIS launch - every lane first stores the rows
 // of x it owns among the slab's first nsend_prev / last nsend_next into the neighbours' ghost granules (system scope: xGMI
 // writes), and a ghost entry is read by polling the own granules for this exchange's epoch.  Same arithmetic, same order.
+// dmask != nullptr: the operator's mask form (dia unused; DiaOffs::cst holds the values).
 template <int EPI, int ND, int RPT, bool HALO, bool XH = false>
 __global__ __launch_bounds__(BS) void k_spmv_dia(DiaOffs o, const double* __restrict__ dia,
+                                                 const uint16_t* __restrict__ dmask,
                                                  int64_t ld, int64_t n, int nblk,
                                                  const double* __restrict__ x,
                                                  const double* __restrict__ ghost, int nprev,
@@ -737,10 +789,12 @@ __global__ __launch_bounds__(BS) void k_spmv_dia(DiaOffs o, const double* __rest
     double s0[RPT], s1[RPT];
 #pragma unroll
     for (int u = 0; u < RPT; ++u) s0[u] = s1[u] = 0.0;
-    auto diagonal = [&](int d) {
+    unsigned msk[RPT];                 // mask form: the presence bits of this lane's row pairs
+    auto diagonal = [&](int d, auto form) {
+        constexpr bool MF = decltype(form)::value;
         const int64_t off = o.off[d];
         const bool even = ((off & 1) == 0) && xal;
-        const double* __restrict__ dd = dia + (int64_t)d * ld;
+        const double c = MF ? o.cst[d] : 0.0;
         double2 a[RPT];
         double x0[RPT], x1[RPT];
         long long gix[XH ? 2 * RPT : 1];       // XH: the ghost entries this lane needs from this diagonal (-1: none)
@@ -748,7 +802,7 @@ __global__ __launch_bounds__(BS) void k_spmv_dia(DiaOffs o, const double* __rest
 #pragma unroll
         for (int u = 0; u < RPT; ++u) {
             const int64_t r = base + 2 * (threadIdx.x + u * BS);   // ld covers the whole grid
-            a[u] = ld_nt2(reinterpret_cast<const double2*>(dd + r));
+            a[u] = dia_slot<MF>(dia, ld, d, r >> 1, MF ? msk[u] : 0u, c);
             int64_t c0 = r + off, c1 = r + 1 + off;
             if (even && c0 >= 0 && c1 <= last) {            // aligned pair of x: one 16-byte load
                 const double2 xv = *reinterpret_cast<const double2*>(x + c0);
@@ -798,11 +852,24 @@ __global__ __launch_bounds__(BS) void k_spmv_dia(DiaOffs o, const double* __rest
             s1[u] = (a[u].y != 0.0) ? s1[u] + p1 : s1[u];
         }
     };
-    if constexpr (ND > 0) {
+    auto diagonals = [&](auto form) {
+        if constexpr (ND > 0) {
 #pragma unroll
-        for (int d = 0; d < ND; ++d) diagonal(d);
+            for (int d = 0; d < ND; ++d) diagonal(d, form);
+        } else {
+            for (int d = 0; d < o.nd; ++d) diagonal(d, form);
+        }
+    };
+    bool masked = false;
+    if constexpr (ND <= KH_DIA_CMAX) masked = dmask != nullptr;     // (wave-uniform: a kernel argument)
+    if (masked) {
+        if constexpr (ND <= KH_DIA_CMAX) {
+#pragma unroll
+            for (int u = 0; u < RPT; ++u) msk[u] = dia_mask_load(dmask, (base >> 1) + threadIdx.x + u * BS);
+            diagonals(std::true_type());
+        }
     } else {
-        for (int d = 0; d < o.nd; ++d) diagonal(d);
+        diagonals(std::false_type());
     }
     double acc = 0.0;
 #pragma unroll
@@ -836,11 +903,12 @@ __global__ __launch_bounds__(BS) void k_spmv_dia(DiaOffs o, const double* __rest
     }
 }
 
-// Banded SpMM: the diagonal-major copy streamed once for DC columns of X (k_spmv_dia's order per column:
+// Banded SpMM: the operator (either form) streamed once for DC columns of X (k_spmv_dia's order per column:
 // ascending offsets, separate multiply and add, empty slots skipped - the same bits).  A lane owns one pair
 // of neighbouring rows and DC accumulator pairs.
 template <int DC>
-__global__ __launch_bounds__(BS) void k_spmm_dia(DiaOffs o, const double* __restrict__ dia, int64_t ld,
+__global__ __launch_bounds__(BS) void k_spmm_dia(DiaOffs o, const double* __restrict__ dia,
+                                                 const uint16_t* __restrict__ dmask, int64_t ld,
                                                  int64_t n, const double* __restrict__ X, int64_t ldx,
                                                  double* __restrict__ Y, int64_t ldy, int nc) {
     const int64_t r = ((int64_t)blockIdx.x * BS + threadIdx.x) * 2;
@@ -849,9 +917,10 @@ __global__ __launch_bounds__(BS) void k_spmm_dia(DiaOffs o, const double* __rest
     double s0[DC], s1[DC];
 #pragma unroll
     for (int j = 0; j < DC; ++j) s0[j] = s1[j] = 0.0;
-    for (int d = 0; d < o.nd; ++d) {
+    auto diagonal = [&](int d, unsigned m, auto form) {
+        constexpr bool MF = decltype(form)::value;
         const int64_t off = o.off[d];
-        const double2 a = ld_nt2(reinterpret_cast<const double2*>(dia + (int64_t)d * ld + r));
+        const double2 a = dia_slot<MF>(dia, ld, d, r >> 1, m, MF ? o.cst[d] : 0.0);
         int64_t c0 = r + off, c1 = r + 1 + off;
         c0 = c0 < 0 ? 0 : (c0 > last ? last : c0);
         c1 = c1 < 0 ? 0 : (c1 > last ? last : c1);
@@ -868,6 +937,12 @@ __global__ __launch_bounds__(BS) void k_spmm_dia(DiaOffs o, const double* __rest
             s0[j] = (a.x != 0.0) ? s0[j] + p0 : s0[j];
             s1[j] = (a.y != 0.0) ? s1[j] + p1 : s1[j];
         }
+    };
+    if (dmask != nullptr) {           // (wave-uniform)
+        const unsigned m = dia_mask_load(dmask, r >> 1);
+        for (int d = 0; d < o.nd; ++d) diagonal(d, m, std::true_type());
+    } else {
+        for (int d = 0; d < o.nd; ++d) diagonal(d, 0u, std::false_type());
     }
 #pragma unroll
     for (int j = 0; j < DC; ++j) {

@@ -124,6 +124,7 @@ struct kh_ctx_s {
     int64_t n_panel_gemm = 0;        // passes of k_panel_gemm_mfma (kh_gemm_nn with 2 ... 16 output columns; the same switch)
     double* gram_part = nullptr;     // [256][KH_GRAM_NB] workgroup partials of k_gram_mfma (allocated at first use)
     int64_t n_zspmv_dia = 0;         // products of a banded complex operator through its diagonal-major copy (zpath.h: k_zspmv_dia)
+    int64_t n_dia_mask = 0;          // launches that read a constant-coefficient banded operator's presence masks (dmask)
     int chain_xr = 1;
     int chain_xr_cus = 0;            // tests: the compute units the shape is chosen for (0: all; two processes share one device)
     int64_t n_chain_xr = 0;
@@ -256,11 +257,15 @@ struct kh_mat_s {
     int nblk = 0;
     int tile = 0;
     double* part = nullptr;     // max(nblk, dia_nblk) partial sums for the fused dot / norm epilogues
-    // banded copy of a CSR operator whose entries sit on <= KH_DIA_MAX diagonals (k_spmv_dia)
-    double* dia = nullptr;      // [dia_nd][dia_ld], 0.0 = no entry
+    // banded copy of a CSR operator whose entries sit on <= KH_DIA_MAX diagonals (k_spmv_dia), in one of two forms:
+    double* dia = nullptr;      // values: [dia_nd][dia_ld], 0.0 = no entry
+    uint16_t* dmask = nullptr;  // constant coefficients (every diagonal holds one value, dia_nd <= 8): [dia_ld / 2] presence
+                                // masks of row pairs (bit d of the low / high byte: row 2 i2 / 2 i2 + 1 has an entry on
+                                // diagonal d) and the value of diagonal d in dia_cst[d]; no value copy then
     int64_t dia_ld = 0;
     int dia_nd = 0, dia_nblk = 0, dia_rpt = 0;
     int dia_off[32] = {0};
+    double dia_cst[8] = {0};
     // the same for a complex CSR operator (round 4): zdia[d][i] as (re, im) pairs, leading dimension in complex entries;
     // dia_nd / dia_off describe it; used by the complex chain kernels' prologue (the stand-alone SpMV stays CSR-stream)
     double* zdia = nullptr;
@@ -288,6 +293,10 @@ struct kh_mat_s {
     int xh_on = 0;                             // the host layer switches it on after EVERY rank has attached (kh_mat_xh_enable)
     int xh_self = 0;                           // loopback: the neighbours' boxes are my own (nothing to close)
 };
+
+// the operator has a banded form (either of the two: value copy or presence masks) that k_spmv_dia and the fused chain
+// prologues read
+static inline bool kh_banded(const kh_mat_s* A) { return A->dia != nullptr || A->dmask != nullptr; }
 
 // true when reductions must be all-reduced / halos exchanged (several ranks, or a 1-rank
 // communicator in forced mode: the multi-rank code path is then testable on a single GPU)

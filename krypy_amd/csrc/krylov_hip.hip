@@ -292,21 +292,29 @@ static void launch_dia_nd(kh_ctx ctx, kh_mat A, const DiaOffs& o, const double* 
             (void)hipHostGetDevicePointer(&dp, ctx->xr_err_pin, 0);
             xh.err = static_cast<int*>(dp);
             hipLaunchKernelGGL((k_spmv_dia<EPI, ND, RPT, true, true>), dim3(grid), dim3(BS), 0, ctx->stream, o, A->dia,
-                               A->dia_ld, A->n_rows, A->dia_nblk, x, A->ghost, (int)A->nrecv_prev, (int)A->nrecv_next, y,
+                               A->dmask, A->dia_ld, A->n_rows, A->dia_nblk, x, A->ghost, (int)A->nrecv_prev, (int)A->nrecv_next, y,
                                aux, A->part, rg.blk_lo, rg.blk_skip, rg.part_off, xh);
             return;
         }
     }
     hipLaunchKernelGGL((k_spmv_dia<EPI, ND, RPT, HALO>), dim3(grid), dim3(BS), 0, ctx->stream, o, A->dia,
-                       A->dia_ld, A->n_rows, A->dia_nblk, x, A->ghost, (int)A->nrecv_prev, (int)A->nrecv_next, y,
+                       A->dmask, A->dia_ld, A->n_rows, A->dia_nblk, x, A->ghost, (int)A->nrecv_prev, (int)A->nrecv_next, y,
                        aux, A->part, rg.blk_lo, rg.blk_skip, rg.part_off, XhArgs());
+}
+
+// the offsets of a banded operator, and - mask form - the values of its diagonals
+static DiaOffs dia_offs(const kh_mat_s* A) {
+    DiaOffs o;
+    o.nd = A->dia_nd;
+    for (int d = 0; d < KH_DIA_MAX; ++d) o.off[d] = d < A->dia_nd ? A->dia_off[d] : 0;
+    for (int d = 0; d < KH_DIA_CMAX; ++d) o.cst[d] = (A->dmask != nullptr && d < A->dia_nd) ? A->dia_cst[d] : 0.0;
+    return o;
 }
 
 template <int EPI>
 static void launch_dia(kh_ctx ctx, kh_mat A, const double* x, double* y, const double* aux, const SpmvRange& rg) {
-    DiaOffs o;
-    o.nd = A->dia_nd;
-    for (int d = 0; d < KH_DIA_MAX; ++d) o.off[d] = d < A->dia_nd ? A->dia_off[d] : 0;
+    const DiaOffs o = dia_offs(A);
+    if (rg.grid != 0) ctx->n_dia_mask += A->dmask != nullptr ? 1 : 0;
     // rows per workgroup = 2 * BS * RPT (fixed at upload: dia_ld covers whole workgroups)
 #define KH_DIA_RPT(R, H)                                                            \
     switch (A->dia_nd) {                                                            \
@@ -323,9 +331,9 @@ static void launch_dia(kh_ctx ctx, kh_mat A, const double* x, double* y, const d
 #undef KH_DIA_RPT
 }
 
-// the banded kernel serves when the operator has a diagonal-major copy (and nobody switched it off)
+// the banded kernel serves when the operator has a banded form (and nobody switched it off)
 static inline bool use_dia(kh_ctx ctx, kh_mat A, const double* y) {
-    return A->dia != nullptr && ctx->spmv_dia && (reinterpret_cast<uintptr_t>(y) & 15) == 0;
+    return kh_banded(A) && ctx->spmv_dia && (reinterpret_cast<uintptr_t>(y) & 15) == 0;
 }
 
 template <int EPI>
@@ -545,7 +553,7 @@ static hipError_t launch_chain_onex(kh_ctx ctx, int G, ChainArgs& a) {
 
 // short vectors without a preconditioner: whole columns in a register ring, requested several links ahead
 // (chain.h, k_mgs_chain_small); ONEX or spread over the chip
-template <int R2, bool MASKED, int FND, bool ONEX>
+template <int R2, bool MASKED, int FND, bool ONEX, bool DMASK = false>
 static hipError_t launch_chain_small(kh_ctx ctx, int G, ChainArgs& a) {
     static int blocks_per_cu = -1;
 #ifndef KH_SMALL_LA4
@@ -553,7 +561,7 @@ static hipError_t launch_chain_small(kh_ctx ctx, int G, ChainArgs& a) {
 #define KH_SMALL_LA8 2
 #endif
     constexpr int LA = (R2 == 4) ? KH_SMALL_LA4 : KH_SMALL_LA8;          // columns requested ahead
-    auto kern = k_mgs_chain_small<R2, LA, MASKED, FND, ONEX>;
+    auto kern = k_mgs_chain_small<R2, LA, MASKED, FND, ONEX, DMASK>;
     if (blocks_per_cu < 0) {
         int nb = 0;
         hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, ONEX ? CH_BS + 64 : CH_BS, 0);
@@ -812,18 +820,19 @@ int try_chain(kh_ctx ctx, kh_vec V, kh_vec B, const double* w, int64_t wld, cons
                     2 * Afuse->n_rows == n && Afuse->nrecv_prev + Afuse->nrecv_next == 0 && 2 * Afuse->zdia_ld >= need_ld;
         } else {
             fused = ctx->chain_spmv && padded && ((a.debug & 3) == 0) && ((r2 >= 16 && r2 <= 48) || want_onex || lz_shape || small_shape) && xk != nullptr &&
-                    Afuse->kind == KH_MAT_CSR && Afuse->dia != nullptr && (Afuse->dia_nd == 5 || Afuse->dia_nd == 7) &&
+                    Afuse->kind == KH_MAT_CSR && kh_banded(Afuse) && (Afuse->dia_nd == 5 || Afuse->dia_nd == 7) &&
                     Afuse->n_rows == n && Afuse->nrecv_prev + Afuse->nrecv_next == 0 && Afuse->dia_ld >= need_ld;
         }
         if (!fused) return 0;
         a.dia = cplx ? Afuse->zdia : Afuse->dia;
+        a.dmask = cplx ? nullptr : Afuse->dmask;
         a.dia_ld = cplx ? Afuse->zdia_ld : Afuse->dia_ld;
         a.xk = xk;
         a.n_last = cplx ? Afuse->n_rows - 1 : n - 1;
-        a.offs.nd = Afuse->dia_nd;
-        for (int d = 0; d < KH_DIA_MAX; ++d) a.offs.off[d] = d < Afuse->dia_nd ? Afuse->dia_off[d] : 0;
+        a.offs = dia_offs(Afuse);
     } else {
         a.dia = nullptr;
+        a.dmask = nullptr;
         a.dia_ld = 0;
         a.xk = nullptr;
         a.n_last = n - 1;
@@ -873,6 +882,7 @@ int try_chain(kh_ctx ctx, kh_vec V, kh_vec B, const double* w, int64_t wld, cons
             if (a.debug == 4) ctx->chain_fault = 0;
             ctx->n_chain += 1;
             ctx->n_chain_fused += 1;
+            ctx->n_dia_mask += a.dmask != nullptr ? 1 : 0;
             ctx->n_lanczos_fused += 1;
             ctx->chain_epoch += 2u;          // the coefficient's and the norm's grid-wide sums
             if (hpin == nullptr)
@@ -926,6 +936,7 @@ int try_chain(kh_ctx ctx, kh_vec V, kh_vec B, const double* w, int64_t wld, cons
                 ctx->n_chain_blk += 1;
                 ctx->n_chain_onex += want_onex ? 1 : 0;
                 ctx->n_chain_fused += fused ? 1 : 0;
+                ctx->n_dia_mask += (fused && a.dmask != nullptr) ? 1 : 0;
                 ctx->n_chain_lds += 1;
                 ctx->chain_epoch += (unsigned)nsums;
                 if (hpin == nullptr)
@@ -939,18 +950,21 @@ int try_chain(kh_ctx ctx, kh_vec V, kh_vec B, const double* w, int64_t wld, cons
             // (kh_ctx_set("chain_blk", 1) forgets it)
             ctx->blk_refused_n = n;
         }
-#define KH_SM(R, X)                                                                                          \
-    (fused ? (a.offs.nd == 5 ? launch_chain_small<R, false, 5, X>(ctx, G, a) : launch_chain_small<R, false, 7, X>(ctx, G, a)) \
+#define KH_SM_F(R, X, M) (a.offs.nd == 5 ? launch_chain_small<R, false, 5, X, M>(ctx, G, a) : launch_chain_small<R, false, 7, X, M>(ctx, G, a))
+#define KH_SM(R, X)                                                                                              \
+    (fused ? (a.dmask != nullptr ? KH_SM_F(R, X, true) : KH_SM_F(R, X, false))                                   \
            : (padded ? launch_chain_small<R, false, 0, X>(ctx, G, a) : launch_chain_small<R, true, 0, X>(ctx, G, a)))
         if (want_onex) e = (r2 == 4) ? KH_SM(4, true) : KH_SM(8, true);
         else e = (r2 == 4) ? KH_SM(4, false) : KH_SM(8, false);
 #undef KH_SM
+#undef KH_SM_F
         if (e == hipSuccess) {
             if (a.debug == 4) ctx->chain_fault = 0;
             ctx->n_chain += 1;
             ctx->n_chain_small += 1;
             ctx->n_chain_onex += want_onex ? 1 : 0;
             ctx->n_chain_fused += fused ? 1 : 0;
+            ctx->n_dia_mask += (fused && a.dmask != nullptr) ? 1 : 0;
             ctx->n_chain_lds += 1;          // (the column is used twice from the chip: counted with the LDS / ring family)
             ctx->chain_epoch += (unsigned)(a.ncol * a.sweeps + 1);
             if (hpin == nullptr)
@@ -983,6 +997,7 @@ int try_chain(kh_ctx ctx, kh_vec V, kh_vec B, const double* w, int64_t wld, cons
             ctx->n_chain += 1;
             ctx->n_chain_onex += 1;
             ctx->n_chain_fused += fused ? 1 : 0;
+            ctx->n_dia_mask += (fused && a.dmask != nullptr) ? 1 : 0;
             ctx->n_chain_lds += pf_ ? 1 : 0;
             ctx->n_chain_pf += pf_ ? 1 : 0;
             ctx->chain_epoch += (unsigned)(a.ncol * a.sweeps + 1);
@@ -1072,6 +1087,7 @@ int try_chain(kh_ctx ctx, kh_vec V, kh_vec B, const double* w, int64_t wld, cons
     ctx->n_chain_long += use_long ? 1 : 0;
     ctx->n_chain_pf += use_pf ? 1 : 0;
     ctx->n_chain_fused += fused ? 1 : 0;
+    ctx->n_dia_mask += (fused && a.dmask != nullptr) ? 1 : 0;
     ctx->chain_epoch += (unsigned)(a.ncol * a.sweeps + 1);   // one grid reduction per link (complex: both parts in it) + the norm
     if (hpin == nullptr)      // (otherwise workgroup 0 has written the error word to the pinned slot itself)
         KH_HIP(hipMemcpyAsync(ctx->chain_err_pin[slot], ctx->chain_err, sizeof(int), hipMemcpyDeviceToHost,
@@ -1695,6 +1711,7 @@ int kh_ctx_get(kh_ctx ctx, const char* key, int64_t* value) {
     else if (!strcmp(key, "n_gram_mfma")) *value = ctx->n_gram_mfma;
     else if (!strcmp(key, "n_panel_gemm")) *value = ctx->n_panel_gemm;
     else if (!strcmp(key, "n_zspmv_dia")) *value = ctx->n_zspmv_dia;
+    else if (!strcmp(key, "n_dia_mask")) *value = ctx->n_dia_mask;
     else if (!strcmp(key, "n_chain_xr")) *value = ctx->n_chain_xr;
     else if (!strcmp(key, "n_blk_rebuild")) *value = ctx->n_blk_rebuild;
     else if (!strcmp(key, "n_blk_rowless")) *value = ctx->n_blk_rowless;
@@ -1922,15 +1939,22 @@ static int build_rowblocks(const int32_t* indptr, int64_t n_rows, int tile,
 // Banded structure (k_spmv_dia): square, columns strictly ascending within each row, no stored
 // zeros, at most KH_DIA_MAX distinct diagonals, and those at least 70 % full (8 B per slot against
 // 12 B per CSR entry).  One pass over the host arrays; gives up at the first violation.
+// cst (real data only): filled with the value of every diagonal, in ascending offset order, when each diagonal's stored
+// values are bitwise equal to its first one and there are at most KH_DIA_CMAX diagonals - the mask form (build_dia);
+// left empty otherwise.
 static bool detect_dia(int64_t n_rows, int64_t n_cols, int64_t nnz, const int32_t* indptr,
                        const int32_t* indices, const double* data, std::vector<int>& offs,
-                       int64_t nprev = 0, int64_t nnext = 0, int cw = 1) {
+                       int64_t nprev = 0, int64_t nnext = 0, int cw = 1, std::vector<double>* cst = nullptr) {
     // cw = 2: complex data, (re, im) pairs - a stored zero is an entry whose two parts are zero
     // nprev / nnext: ghost columns of a block-row shard, taken as the rows before / after the slab
     offs.clear();
+    if (cst != nullptr) cst->clear();
     if (n_rows + nprev + nnext != n_cols || n_rows < 2 || nnz == 0 || data == nullptr) return false;
     if (nnz > (int64_t)KH_DIA_MAX * n_rows) return false;
+    // per diagonal (moved along with its offset: the table reorders): the bits of its first value, still constant?
     int tab[KH_DIA_MAX];
+    uint64_t tbits[KH_DIA_MAX];
+    bool tconst[KH_DIA_MAX];
     int nd = 0;
     for (int64_t r = 0; r < n_rows; ++r) {
         int prev = 0;
@@ -1939,23 +1963,48 @@ static bool detect_dia(int64_t n_rows, int64_t n_cols, int64_t nnz, const int32_
             if ((p > indptr[r] && c <= prev) || (data[p * cw] == 0.0 && (cw == 1 || data[p * cw + 1] == 0.0))) return false;
             prev = c;
             const int off = c - (int)r;
+            uint64_t bits;
+            memcpy(&bits, data + p * cw, sizeof(bits));
             int d = 0;
             while (d < nd && tab[d] != off) ++d;
             if (d == nd) {
                 if (nd == KH_DIA_MAX) return false;
-                tab[nd++] = off;
-            } else if (d > 0) {            // move-to-front keeps the common offsets cheap to find
-                std::swap(tab[d], tab[d - 1]);
+                tab[nd] = off;
+                tbits[nd] = bits;
+                tconst[nd] = true;
+                ++nd;
+            } else {
+                tconst[d] = tconst[d] && tbits[d] == bits;
+                if (d > 0) {               // move-to-front keeps the common offsets cheap to find
+                    std::swap(tab[d], tab[d - 1]);
+                    std::swap(tbits[d], tbits[d - 1]);
+                    std::swap(tconst[d], tconst[d - 1]);
+                }
             }
         }
     }
     if ((double)nnz < 0.7 * (double)nd * (double)n_rows) return false;
     offs.assign(tab, tab + nd);
     std::sort(offs.begin(), offs.end());
+    if (cst != nullptr && cw == 1 && nd <= KH_DIA_CMAX) {
+        bool all = true;
+        for (int d = 0; d < nd; ++d) all = all && tconst[d];
+        if (all) {
+            cst->resize(nd);
+            for (int j = 0; j < nd; ++j) {        // (offsets are distinct: one slot of the table each)
+                int d = 0;
+                while (tab[d] != offs[j]) ++d;
+                memcpy(&(*cst)[j], &tbits[d], sizeof(double));
+            }
+        }
+    }
     return true;
 }
 
-static int build_dia(kh_ctx ctx, kh_mat A, const std::vector<int>& offs, bool halo = false) {
+// cst non-empty (detect_dia: constant coefficients): the mask form - presence masks of the row pairs and the nd values,
+// no value copy; otherwise the diagonal-major copy of the values
+static int build_dia(kh_ctx ctx, kh_mat A, const std::vector<int>& offs, const std::vector<double>& cst,
+                     bool halo = false) {
     static int mode = -2;     // KRYPY_AMD_SPMV_DIA: 0 = off, 1/2/4 = row pairs per lane (default 4)
     if (mode == -2) {
         const char* e = getenv("KRYPY_AMD_SPMV_DIA");
@@ -1970,21 +2019,48 @@ static int build_dia(kh_ctx ctx, kh_mat A, const std::vector<int>& offs, bool ha
     // the chain kernel's fused prologue (chain.h) can read every diagonal without a predicate
     const int64_t ld = ((std::max(nblk * rows_per_wg, padded_ld(ctx, A->n_rows)) + rows_per_wg - 1) / rows_per_wg) *
                        rows_per_wg;
-    const size_t bytes = sizeof(double) * (size_t)ld * offs.size();
-    double* dia = nullptr;
-    if (hipMalloc(&dia, bytes) != hipSuccess) {     // no room for the copy: the CSR kernel serves
-        (void)hipGetLastError();
-        return 0;
-    }
-    KH_HIP(hipMemsetAsync(dia, 0, bytes, ctx->stream));
     DiaOffs o;
     o.nd = (int)offs.size();
     for (int d = 0; d < KH_DIA_MAX; ++d) o.off[d] = d < o.nd ? offs[d] : 0;
-    hipLaunchKernelGGL(k_dia_fill, dim3((unsigned)((A->n_rows + BS - 1) / BS)), dim3(BS), 0, ctx->stream,
-                       A->indptr, A->indices, A->data, A->n_rows, (int)A->nrecv_prev, o, dia, ld);
-    KH_HIP(hipGetLastError());
+    const bool masked = !cst.empty() && o.nd <= KH_DIA_CMAX;
+    for (int d = 0; d < KH_DIA_CMAX; ++d) o.cst[d] = (masked && d < o.nd) ? cst[d] : 0.0;
+    if (masked) {
+        // ld is even (whole workgroups of row pairs): ld / 2 masks, every one written by the fill kernel
+        const int64_t npair = ld / 2;
+        uint16_t* mask = nullptr;
+        if (hipMalloc(&mask, sizeof(uint16_t) * (size_t)npair) != hipSuccess) {   // no room: the CSR kernel serves
+            (void)hipGetLastError();
+            return 0;
+        }
+        hipLaunchKernelGGL(k_dia_mask_fill, dim3((unsigned)((npair + BS - 1) / BS)), dim3(BS), 0, ctx->stream,
+                           A->indptr, A->indices, A->n_rows, (int)A->nrecv_prev, o, mask, npair);
+        const hipError_t e = hipGetLastError();
+        if (e == hipSuccess) {
+            A->dmask = mask;
+        } else {
+            (void)hipFree(mask);
+            KH_HIP(e);
+        }
+        for (int d = 0; d < o.nd; ++d) A->dia_cst[d] = cst[d];
+    } else {
+        const size_t bytes = sizeof(double) * (size_t)ld * offs.size();
+        double* dia = nullptr;
+        if (hipMalloc(&dia, bytes) != hipSuccess) {     // no room for the copy: the CSR kernel serves
+            (void)hipGetLastError();
+            return 0;
+        }
+        KH_HIP(hipMemsetAsync(dia, 0, bytes, ctx->stream));
+        hipLaunchKernelGGL(k_dia_fill, dim3((unsigned)((A->n_rows + BS - 1) / BS)), dim3(BS), 0, ctx->stream,
+                           A->indptr, A->indices, A->data, A->n_rows, (int)A->nrecv_prev, o, dia, ld);
+        const hipError_t e = hipGetLastError();
+        if (e == hipSuccess) {
+            A->dia = dia;
+        } else {
+            (void)hipFree(dia);
+            KH_HIP(e);
+        }
+    }
     KH_HIP(hipStreamSynchronize(ctx->stream));
-    A->dia = dia;
     A->dia_ld = ld;
     A->dia_nd = o.nd;
     A->dia_nblk = (int)nblk;
@@ -2013,7 +2089,9 @@ int dia_rebuild_for_halo(kh_ctx ctx, kh_mat A) {
     }
     (void)hipStreamSynchronize(ctx->stream);
     (void)hipFree(A->dia);
+    (void)hipFree(A->dmask);
     A->dia = nullptr;
+    A->dmask = nullptr;
     A->dia_nd = 0;
     A->dia_nblk = 0;
     if (A->nnz == 0) return 0;
@@ -2041,8 +2119,9 @@ int dia_rebuild_for_halo(kh_ctx ctx, kh_mat A) {
         A->csr_b1 = std::max(b1, b0);
     }
     std::vector<int> offs;
+    std::vector<double> cst;
     if (!detect_dia(A->n_rows, A->n_cols, A->nnz, indptr.data(), indices.data(), data.data(), offs,
-                    A->nrecv_prev, A->nrecv_next))
+                    A->nrecv_prev, A->nrecv_next, 1, &cst))
         return 0;
     const int64_t need = (A->n_rows + 2 * BS - 1) / (2 * BS);
     if (need > std::max(A->nblk, 1)) {           // partial sums of the fused epilogues: one per workgroup
@@ -2050,8 +2129,8 @@ int dia_rebuild_for_halo(kh_ctx ctx, kh_mat A) {
         A->part = nullptr;
         KH_HIP(hipMalloc(&A->part, sizeof(double) * need));
     }
-    KH_TRY(build_dia(ctx, A, offs, true));
-    if (A->dia != nullptr) {
+    KH_TRY(build_dia(ctx, A, offs, cst, true));
+    if (kh_banded(A)) {
         const int64_t rows_per_wg = 2 * (int64_t)BS * A->dia_rpt;
         A->dia_b0 = (int)std::min<int64_t>((bnd_lo + rows_per_wg - 1) / rows_per_wg, A->dia_nblk);
         A->dia_b1 = (int)std::max<int64_t>(bnd_hi / rows_per_wg, A->dia_b0);
@@ -2125,7 +2204,8 @@ int kh_csr_upload(kh_ctx ctx, int64_t n_rows, int64_t n_cols, int64_t nnz, const
         KH_HIP(hipMalloc(&A->data, sizeof(double) * std::max<int64_t>(nnz, 1)));
         KH_HIP(hipMalloc(&A->rowblk, sizeof(int32_t) * blk.size()));
         std::vector<int> offs;
-        const bool banded = detect_dia(n_rows, n_cols, nnz, indptr, indices, data, offs);
+        std::vector<double> cst;
+        const bool banded = detect_dia(n_rows, n_cols, nnz, indptr, indices, data, offs, 0, 0, 1, &cst);
         const int64_t npart = std::max<int64_t>(std::max(A->nblk, 1), banded ? (n_rows + 2 * BS - 1) / (2 * BS) : 1   /* RPT >= 1 */);
         KH_HIP(hipMalloc(&A->part, sizeof(double) * npart));
         KH_HIP(hipMemcpy(A->indptr, indptr, sizeof(int32_t) * (n_rows + 1), hipMemcpyHostToDevice));
@@ -2134,7 +2214,7 @@ int kh_csr_upload(kh_ctx ctx, int64_t n_rows, int64_t n_cols, int64_t nnz, const
             KH_HIP(hipMemcpy(A->data, data, sizeof(double) * nnz, hipMemcpyHostToDevice));
         }
         KH_HIP(hipMemcpy(A->rowblk, blk.data(), sizeof(int32_t) * blk.size(), hipMemcpyHostToDevice));
-        if (banded) KH_TRY(build_dia(ctx, A, offs));
+        if (banded) KH_TRY(build_dia(ctx, A, offs, cst));
         // the columns every row block touches (k_spmv_stream<.., WIN>): where nine blocks in ten fit an LDS window of at most
         // SPMV_WIN_CAP entries of x, the operator's launches carry a window as wide as the widest of those
         if (A->nblk > 0 && nnz > 0) {
@@ -2278,6 +2358,7 @@ int kh_mat_free(kh_mat A) {
     (void)hipFree(A->blkwin);
     (void)hipFree(A->part);
     (void)hipFree(A->dia);
+    (void)hipFree(A->dmask);
     (void)hipFree(A->zdia);
     (void)hipFree(A->a);
     (void)hipFree(A->diag);
@@ -2288,7 +2369,7 @@ int kh_mat_free(kh_mat A) {
     return 0;
 }
 
-int kh_mat_diagonals(kh_mat A) { return (A != nullptr && A->dia != nullptr) ? A->dia_nd : 0; }
+int kh_mat_diagonals(kh_mat A) { return (A != nullptr && kh_banded(A)) ? A->dia_nd : 0; }
 
 int kh_apply(kh_ctx ctx, kh_mat A, kh_vec X, int64_t xcol, kh_vec Y, int64_t ycol, int64_t ncols) {
     KH_ARG(ctx && A, "kh_apply: NULL handle");
@@ -2335,14 +2416,13 @@ int kh_apply(kh_ctx ctx, kh_mat A, kh_vec X, int64_t xcol, kh_vec Y, int64_t yco
         }
         if (!shard && use_dia(ctx, A, Y->col(ycol)) && (Y->ld & 1) == 0) {
             constexpr int DC = 8;
-            DiaOffs o;
-            o.nd = A->dia_nd;
-            for (int d = 0; d < KH_DIA_MAX; ++d) o.off[d] = d < A->dia_nd ? A->dia_off[d] : 0;
+            const DiaOffs o = dia_offs(A);
             const unsigned grid = (unsigned)((A->n_rows + 2 * BS - 1) / (2 * BS));
             for (int64_t c = 0; c < ncols; c += DC) {
                 const int nc = (int)std::min<int64_t>(DC, ncols - c);
-                hipLaunchKernelGGL((k_spmm_dia<DC>), dim3(grid), dim3(BS), 0, ctx->stream, o, A->dia, A->dia_ld,
-                                   A->n_rows, X->col(xcol + c), X->ld, Y->col(ycol + c), Y->ld, nc);
+                hipLaunchKernelGGL((k_spmm_dia<DC>), dim3(grid), dim3(BS), 0, ctx->stream, o, A->dia, A->dmask,
+                                   A->dia_ld, A->n_rows, X->col(xcol + c), X->ld, Y->col(ycol + c), Y->ld, nc);
+                ctx->n_dia_mask += A->dmask != nullptr ? 1 : 0;
             }
             KH_HIP(hipGetLastError());
             ctx->n_spmm += 1;
@@ -2755,7 +2835,7 @@ int kh_arnoldi_step_begin(kh_ctx ctx, kh_mat A, kh_proj proj, kh_mat Md, kh_vec 
     if (A != nullptr) {
         KH_ARG(A->n_rows == n, "kh_arnoldi_step: operator rows %lld != %lld", (long long)A->n_rows,
                (long long)n);
-        if (want_chain && proj == nullptr && A->kind == KH_MAT_CSR && A->dia != nullptr && ctx->spmv_dia) {
+        if (want_chain && proj == nullptr && A->kind == KH_MAT_CSR && kh_banded(A) && ctx->spmv_dia) {
             // banded operator: the chain kernel computes w = A v_k in its prologue (no SpMV launch, w
             // never touches HBM); returns 0 when that instantiation does not apply
             // a deferred MINRES update of an earlier iteration rides along when the step runs as the three-pass

@@ -6,7 +6,7 @@
 // Jacobi diagonal and w's own bytes pass by more often than needed (1.04 GB at N = 10^7, 4.9 TB/s: the launch is
 // bound by its phase boundaries, not by HBM).  A step has ONE Gram-Schmidt link, so nothing forces that split:
 //
-//   pass 1   row by row: (A v_k)_r from the diagonal-major copy (as k_spmv_dia / chain_apply_banded compute it),
+//   pass 1   row by row: (A v_k)_r from the banded form (as k_spmv_dia / chain_apply_banded compute it),
 //            minus h_{k-1,k} p_{k-1}[r], into the register that holds w_r; the same row of v_k - its cache line was
 //            just gathered for the operator - feeds <v_k, w> at once                      (dia + v_k + p_{k-1})
 //   sum      alpha = <v_k, w>
@@ -83,44 +83,52 @@ __global__ __launch_bounds__(CH_BS) void k_lanczos_fused(ChainArgs a, MinresJob 
         const double2* __restrict__ p2 = reinterpret_cast<const double2*>(a.bprev);
         const double2* __restrict__ v2 = reinterpret_cast<const double2*>(a.V + a.col0 * a.ld);
         const int64_t last = a.n_last;
-        int64_t fb = first;          // (row r at a constant distance from the opaque base: chain.h, chain_apply_banded)
+        // the operator's form: one wave-uniform branch around two straight-line copies of the row loop (chain.h,
+        // chain_apply_banded)
+        auto pass1 = [&](auto form) {
+            constexpr bool MASK = decltype(form)::value;
+            int64_t fb = first;          // (row r at a constant distance from the opaque base: chain.h, chain_apply_banded)
 #pragma unroll
-        for (int r = 0; r < R2; ++r) {
-            const int64_t i2 = fb + (int64_t)r * CH_BS;
-            const int64_t row = 2 * i2;
-            double2 av[FND];
-            double x0[FND], x1[FND];
+            for (int r = 0; r < R2; ++r) {
+                const int64_t i2 = fb + (int64_t)r * CH_BS;
+                const int64_t row = 2 * i2;
+                double2 av[FND];
+                double x0[FND], x1[FND];
+                const unsigned m = MASK ? dia_mask_load(a.dmask, i2) : 0u;
 #pragma unroll
-            for (int d = 0; d < FND; ++d) {
-                const int64_t off = a.offs.off[d];
-                av[d] = ld_nt2(reinterpret_cast<const double2*>(a.dia + (int64_t)d * a.dia_ld) + i2);
-                int64_t c0 = row + off, c1 = row + 1 + off;
-                c0 = c0 < 0 ? 0 : (c0 > last ? last : c0);
-                c1 = c1 < 0 ? 0 : (c1 > last ? last : c1);
-                x0[d] = xk[c0];
-                x1[d] = xk[c1];
+                for (int d = 0; d < FND; ++d) {
+                    const int64_t off = a.offs.off[d];
+                    av[d] = dia_slot<MASK>(a.dia, a.dia_ld, d, i2, m, MASK ? a.offs.cst[d] : 0.0);
+                    int64_t c0 = row + off, c1 = row + 1 + off;
+                    c0 = c0 < 0 ? 0 : (c0 > last ? last : c0);
+                    c1 = c1 < 0 ? 0 : (c1 > last ? last : c1);
+                    x0[d] = xk[c0];
+                    x1[d] = xk[c1];
+                }
+                // (tried: aligned 16-byte loads of x for the even offsets of a stencil pattern, the +-1 neighbours from the
+                // centre pair - 7 load instructions per row pair instead of 12: pass 1 went from 110 to 127 us, not kept;
+                // the MINRES job's six streams interleaved with this loop to fill its bubbles, 19 rows of w in LDS to make
+                // room: 213 us for the pair against 108 + 73 apart, not kept either)
+                const double2 vv = v2[i2];               // (the line the operator's centre entries came from)
+                const double2 pp = ld_nt2(p2 + i2);
+                double s0 = 0.0, s1 = 0.0;
+#pragma unroll
+                for (int d = 0; d < FND; ++d) {
+                    const double q0 = av[d].x * x0[d], q1 = av[d].y * x1[d];
+                    s0 = (av[d].x != 0.0) ? s0 + q0 : s0;
+                    s1 = (av[d].y != 0.0) ? s1 + q1 : s1;
+                }
+                double2 t;
+                t.x = s0 - hk * pp.x;
+                t.y = s1 - hk * pp.y;
+                W_PUT(r, t);
+                acc0 = fma(vv.x, t.x, acc0);
+                acc1 = fma(vv.y, t.y, acc1);
+                if ((r & KH_RIF) == KH_RIF) asm volatile("" : "+v"(fb) : : "memory");   // four rows of loads in flight
             }
-            // (tried: aligned 16-byte loads of x for the even offsets of a stencil pattern, the +-1 neighbours from the
-            // centre pair - 7 load instructions per row pair instead of 12: pass 1 went from 110 to 127 us, not kept;
-            // the MINRES job's six streams interleaved with this loop to fill its bubbles, 19 rows of w in LDS to make
-            // room: 213 us for the pair against 108 + 73 apart, not kept either)
-            const double2 vv = v2[i2];               // (the line the operator's centre entries came from)
-            const double2 pp = ld_nt2(p2 + i2);
-            double s0 = 0.0, s1 = 0.0;
-#pragma unroll
-            for (int d = 0; d < FND; ++d) {
-                const double q0 = av[d].x * x0[d], q1 = av[d].y * x1[d];
-                s0 = (av[d].x != 0.0) ? s0 + q0 : s0;
-                s1 = (av[d].y != 0.0) ? s1 + q1 : s1;
-            }
-            double2 t;
-            t.x = s0 - hk * pp.x;
-            t.y = s1 - hk * pp.y;
-            W_PUT(r, t);
-            acc0 = fma(vv.x, t.x, acc0);
-            acc1 = fma(vv.y, t.y, acc1);
-            if ((r & KH_RIF) == KH_RIF) asm volatile("" : "+v"(fb) : : "memory");   // four rows of loads in flight
-        }
+        };
+        if (a.dmask != nullptr) pass1(std::true_type());
+        else pass1(std::false_type());
     }
     // ---- pass 2: w -= alpha p_k, <w, D w>; a two-deep ring of PB2 rows, its first batch in flight across the sum ----
     constexpr int PB2 = 4, NB2 = R2 / PB2;

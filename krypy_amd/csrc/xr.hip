@@ -264,7 +264,7 @@ int kh_mat_xh_enable(kh_ctx ctx, kh_mat A, int on) {
     KH_ARG(ctx && A, "kh_mat_xh_enable: NULL");
     if (on) {
         KH_ARG(A->xh_box != nullptr, "kh_mat_xh_enable: kh_mat_xh_export / _attach first");
-        KH_ARG(A->dia != nullptr, "kh_mat_xh_enable: the banded kernel carries the exchange; this shard has no diagonal-major copy");
+        KH_ARG(kh_banded(A), "kh_mat_xh_enable: the banded kernel carries the exchange; this shard has no banded form");
         KH_ARG((A->nsend_prev == 0 || A->xh_prev != nullptr) && (A->nsend_next == 0 || A->xh_next != nullptr),
                "kh_mat_xh_enable: a neighbour this slab sends to is not attached");
         if (ctx->xr_err_pin == nullptr) {
