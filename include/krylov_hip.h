@@ -157,6 +157,12 @@ int kh_vec_get(kh_vec v, int64_t col, int64_t i0, int64_t count, double* out);
 int kh_vec_set(kh_vec v, int64_t col, int64_t i0, int64_t count, const double* in);
 /* zero entries [i0, i0+count) of one column */
 int kh_vec_zero_range(kh_vec v, int64_t col, int64_t i0, int64_t count);
+/* diagnostic: *count = how many doubles of the block's padding - rows [n, ld) of every column and the slack the
+ * allocation keeps behind the last column - are not +-0.0 (a NaN counts).  The kernels that run without a row
+ * predicate rely on that padding being zero, and nothing else in this interface can read it (kh_vec_get and
+ * kh_vec_download stop at row n).  Synchronous: waits for the stream, copies the padding strips to the host and counts
+ * there. */
+int kh_vec_padding_nonzero(kh_vec v, int64_t* count);
 
 /* ---- operators (replace MatrixLinearOperator._dot -> A.dot(X), utils.py:1593-1594) --- */
 /* CSR as SciPy holds it: int32 indptr[n_rows+1], int32 indices[nnz] (sorted or not), fp64 data.

@@ -82,6 +82,7 @@ _SIGNATURES = {
     "kh_vec_get": [_H, _I64, _I64, _I64, _c_double_p],
     "kh_vec_set": [_H, _I64, _I64, _I64, _c_double_p],
     "kh_vec_zero_range": [_H, _I64, _I64, _I64],
+    "kh_vec_padding_nonzero": [_H, _c_int64_p],
     "kh_csr_upload": [_H, _I64, _I64, _I64, _c_int32_p, _c_int32_p, _c_double_p,
                       ctypes.POINTER(_H)],
     "kh_dense_upload": [_H, _I64, _I64, _c_double_p, _I64, ctypes.POINTER(_H)],
@@ -284,7 +285,11 @@ class DeviceVectors(object):
     def __init__(self, ctx, n, ncols, dtype=_F64, zero=True):
         """``zero=False``: the caller writes every column before it reads it (a Krylov basis), so a
         recycled block is handed out as it is - only its padding is guaranteed to be zero (no kernel
-        ever writes there).  A fresh allocation is zero-filled either way."""
+        ever writes there).  A fresh allocation is zero-filled either way.  One word is outside that
+        guarantee: for an odd ``n``, row ``n`` of a column an Arnoldi step wrote is ``0 / h`` - NaN when
+        the step broke down with ``h == 0`` exactly, until that column is cleared with :meth:`zero`
+        (which covers the padding), as ``utils.Arnoldi`` does for an invariant subspace
+        (tests/test_gpu_poison.py holds both contracts on the device)."""
         self.ctx, self.n, self.ncols = ctx, int(n), int(ncols)
         self.dtype = _block_dtype(dtype)
         self._w = 2 if self.dtype == _C128 else 1      # doubles per entry
@@ -365,6 +370,14 @@ class DeviceVectors(object):
     def zero_range(self, col, i0, count):
         _check(self.ctx._lib, self.ctx._lib.kh_vec_zero_range(self.handle, col, i0 * self._w,
                                                               count * self._w), "kh_vec_zero_range")
+
+    def padding_nonzero(self):
+        """Diagnostic: how many doubles of the padding (rows ``[n, ld)`` of every column, the slack behind the last
+        one) are not zero (``kh_vec_padding_nonzero``; a NaN counts).  No kernel may ever write there."""
+        out = _I64(0)
+        _check(self.ctx._lib, self.ctx._lib.kh_vec_padding_nonzero(self.handle, ctypes.byref(out)),
+               "kh_vec_padding_nonzero")
+        return out.value
 
 
 def _blas_drotg_address():

@@ -634,6 +634,12 @@ __device__ __forceinline__ double onex_sum_comm(unsigned epoch, unsigned long lo
 // Every vector this kernel reads is a kh_vec / diag buffer allocated with CH_SLACK zeroed doubles
 // behind its last column, so loads need no clamping: an out-of-range lane reads finite data of a
 // neighbouring chunk/column (or zeros) and its w stays exactly 0 (select on registers).
+// Both halves of that sentence are held by tests/test_gpu_poison.py: the runs on blocks whose every column is NaN have the
+// bits of the runs on zeroed blocks ("finite" is not needed: what such a lane reads never reaches a result), and the
+// padding - rows [n, ld) and the slack - is still zero after every sequence (kh_vec_padding_nonzero).  ONE word is outside
+// the second contract: with an odd n, row n shares its 16-byte row with row n - 1 and is stored with it as w_n / h = 0 / h,
+// which is 0 unless the step broke down with h == 0 exactly - then it is NaN like every valid row of that column, until the
+// caller that sees h == 0 clears the column (kh_vec_zero works on all ld rows; Arnoldi.advance and Arnoldi._settle do that).
 constexpr int64_t CH_SLACK = 2 * 48 * (int64_t)CH_BS;  // doubles: one workgroup chunk (<= 40 rows of CH_BS double2) + margin
 
 // Software pipeline: the rows a thread owns are streamed in batches of PB rows through a two-deep

@@ -1824,6 +1824,31 @@ int kh_vec_shape(kh_vec v, int64_t* n, int64_t* ncols, int64_t* ld) {
     return 0;
 }
 
+// diagnostic: the padding of a block (rows [n, ld) of every column, the CH_SLACK doubles behind the last one) on the host,
+// counted there - no kernel, nothing any product path calls
+int kh_vec_padding_nonzero(kh_vec v, int64_t* count) {
+    KH_ARG(v != nullptr && count != nullptr, "kh_vec_padding_nonzero: NULL");
+    KH_HIP(hipStreamSynchronize(v->ctx->stream));
+    const int64_t ncols = std::max<int64_t>(v->ncols, 1);      // (what kh_vec_alloc allocates)
+    const int64_t rows = v->ncols > 0 ? v->n : 0;              // (a block without columns is padding only)
+    const int64_t pad = v->ld - rows;
+    int64_t bad = 0;
+    auto tally = [&bad](const std::vector<double>& h) {
+        for (double x : h) bad += !(x == 0.0);
+    };
+    if (pad > 0) {
+        std::vector<double> h((size_t)pad * (size_t)ncols);
+        KH_HIP(hipMemcpy2D(h.data(), pad * sizeof(double), v->d + rows, v->ld * sizeof(double), pad * sizeof(double),
+                           (size_t)ncols, hipMemcpyDeviceToHost));
+        tally(h);
+    }
+    std::vector<double> tail((size_t)CH_SLACK);
+    KH_HIP(hipMemcpy(tail.data(), v->d + v->ld * ncols, sizeof(double) * CH_SLACK, hipMemcpyDeviceToHost));
+    tally(tail);
+    *count = bad;
+    return 0;
+}
+
 int kh_vec_upload(kh_vec v, int64_t col0, int64_t ncols, const double* host, int64_t host_ld) {
     KH_TRY(check_vec(v, col0, ncols, "kh_vec_upload"));
     chain_blk_touch(v->ctx, v);

@@ -79,6 +79,9 @@ class NumpyVectors(object):
     def zero_range(self, col, i0, count):
         self.a[i0: i0 + count, col] = 0.0
 
+    def padding_nonzero(self):
+        return 0        # (an ndarray has no padding)
+
 
 class NumpyMatrix(object):
     def __init__(self, ctx, kind, mat, shape):

@@ -662,3 +662,97 @@ def test_enable_xr_is_all_or_nothing():
             assert c.on == (fail is None), (fail, r)
             if fail is not None and c.on is False and fail != "export":
                 assert c.detached or r == failing_rank or fail == "attach", (fail, r)
+
+
+def test_poison_helpers_without_a_device(cpu_double):
+    """tests/support/poison.py where there is no GPU.  (i) arnoldi_longdouble - new code that reads neither oracle/ nor
+    the library - reproduces the fp64 oracle's Arnoldi on a small Laplacian far below the bars the GPU tests hold the
+    kernels to (H at 1e-13, the basis at 1e-12): plain and double sweep, Jacobi two-block form, Lanczos; complex data:
+    a real problem in complex storage gives the oracle's numbers with zero imaginary parts, and a complex operator
+    fulfils the Arnoldi relation and orthonormality in extended precision.  (ii) poisoned_allocations on the NumPy double:
+    every zero=False block is filled, the solve inside the `with` has the bits of the solve outside, the original
+    alloc is back afterwards - also after an exception - and bits_equal tells a NaN from the same NaN elsewhere."""
+    import numpy as np
+    import scipy.sparse as sp
+
+    from krypy_amd import linsys, utils
+    from oracle import krylov_ref as ref
+    from tests.support import poison as po
+
+    A = ref.laplace2d(24, 19)
+    n = A.shape[0]
+    rng = np.random.default_rng(7)
+    v = rng.standard_normal(n)
+    dj = np.linspace(0.5, 1.5, n)
+    m = 9
+    for ortho, use_m in (("mgs", False), ("dmgs", False), ("mgs", True), ("lanczos", False), ("lanczos", True)):
+        st = ref.arnoldi_init(A, v, m, ortho=ortho, M=sp.diags(dj).tocsr() if use_m else None)
+        for _ in range(m):
+            ref.arnoldi_step(st)
+        H, V, P = po.arnoldi_longdouble(A, v, m, 2 if ortho == "dmgs" else 1, M_diag=dj if use_m else None,
+                                        lanczos=ortho == "lanczos")
+        assert H.dtype == np.longdouble and V.dtype == np.longdouble
+        assert np.linalg.norm((H - st.H).astype(float)) <= 1e-13 * np.linalg.norm(st.H), (ortho, use_m)
+        assert np.linalg.norm((V - st.V).astype(float)) <= 1e-12, (ortho, use_m)
+        if use_m:
+            assert np.linalg.norm((P - st.P).astype(float)) <= 1e-12, (ortho, use_m)
+    # one step with two sweeps among single ones, as the GPU cases run it
+    Hs, _, _ = po.arnoldi_longdouble(A, v, m, [2 if k == 3 else 1 for k in range(m)])
+    st = ref.arnoldi_init(A, v, m)
+    for _ in range(m):
+        ref.arnoldi_step(st)
+    assert np.linalg.norm((Hs - st.H).astype(float)) <= 1e-13 * np.linalg.norm(st.H)
+    # complex
+    Hz, Vz, _ = po.arnoldi_longdouble(A, v.astype(complex), m, 1)
+    assert Hz.dtype == np.clongdouble and np.all(Hz.imag == 0) and np.all(Vz.imag == 0)
+    assert np.linalg.norm((Hz.real - st.H).astype(float)) <= 1e-13 * np.linalg.norm(st.H)
+    Az = (A + 0.3j * sp.diags(rng.standard_normal(n))).tocsr()
+    vz = v + 1j * rng.standard_normal(n)
+    Hz, Vz, _ = po.arnoldi_longdouble(Az, vz, m, 1)
+    AV = np.stack([po._apply_by_diagonals(Az, Vz[:, k]) for k in range(m)], axis=1)
+    assert np.linalg.norm(AV - Vz.dot(Hz)) <= 1e-17 * np.linalg.norm(Hz) * m
+    assert np.linalg.norm(Vz.conj().T.dot(Vz) - np.eye(m + 1)) <= 1e-15
+    assert np.linalg.norm(AV.astype(complex) - Az.dot(Vz[:, :m].astype(complex))) <= 1e-14 * np.linalg.norm(Hz.astype(complex))
+
+    # bits_equal
+    a = np.array([1.0, np.nan, -0.0])
+    assert po.bits_equal(a, a.copy())
+    for other in (np.array([1.0, np.nan, 0.0]), np.array([np.nan, 1.0, -0.0])):
+        with pytest.raises(AssertionError, match="first at"):
+            po.bits_equal(a, other)
+    with pytest.raises(AssertionError):
+        po.bits_equal(a, a[:2])
+
+    # poisoned_allocations on the NumPy double
+    b = rng.standard_normal(n)
+
+    def solve():
+        try:
+            return linsys.Gmres(linsys.LinearSystem(A, b, M=sp.diags(1.0 / A.diagonal()).tocsr()), maxiter=15, tol=1e-12,
+                                store_arnoldi=True)
+        except utils.ConvergenceError as e:
+            return e.solver
+
+    want = solve()
+    assert "alloc" not in cpu_double.__dict__
+    with po.poisoned_allocations(cpu_double) as rec:
+        got = solve()
+        assert rec.poisoned >= 2                 # (V and P of the preconditioned Arnoldi)
+        live = rec.live()
+        assert live and all(blk.padding_nonzero() == 0 for blk in live)
+        blk = cpu_double.alloc(5, 3, zero=False)
+        assert np.all(np.isnan(blk.download()))
+        assert not np.any(np.isnan(cpu_double.alloc(5, 3).download()))
+        po.poison(blk, cols=[1], value=np.inf)
+        assert np.all(np.isinf(blk.download(1, 1))) and np.all(np.isnan(blk.download(2, 1)))
+    assert "alloc" not in cpu_double.__dict__
+    po.bits_equal(np.array(got.resnorms), np.array(want.resnorms), "resnorms")
+    po.bits_equal(np.array(got.xk), np.array(want.xk), "xk")
+    po.bits_equal(np.array(got.H), np.array(want.H), "H")
+    po.bits_equal(np.array(got.V), np.array(want.V), "V")
+    with pytest.raises(RuntimeError):
+        with po.poisoned_allocations(cpu_double):
+            raise RuntimeError("inside")
+    assert "alloc" not in cpu_double.__dict__
+    z = po.poison(cpu_double.alloc(4, 2, dtype=complex))
+    assert np.all(np.isnan(z.download().real)) and np.all(np.isnan(z.download().imag))
