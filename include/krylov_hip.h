@@ -76,7 +76,8 @@ int kh_ctx_tune(kh_ctx ctx, int reduce_blocks, int spmv_tile);
  * initial values): "spmv_dia" banded SpMV for stencil CSR operators, "chain" register-resident MGS chain,
  * "chain_lds" column head parked in LDS, "chain_spmv" operator fused into the chain prologue, "chain_onex" short vectors
  * on one XCD, "chain_small" the column-ring kernel for them, "lanczos_fused" the three-pass Lanczos kernel, "tag_wait"
- * completion tags in pinned memory instead of an event per Arnoldi step.  bench.py
+ * completion tags in pinned memory instead of an event per Arnoldi step, "house_chain" the one-launch Householder step
+ * (kh_house_step_begin; 0: the caller's per-reflector path).  bench.py
  * uses it to time the CSR-stream and the banded SpMV kernel on the same operator.  Test-only switches (0 by
  * default): "chain_fault" the next chain launch fakes a timeout, "halo_loopback" a 1-rank communicator exchanges
  * the halo of a sharded operator with ITSELF (grouped ncclSend / ncclRecv to its own rank: the slab of an operator
@@ -260,6 +261,28 @@ int kh_arnoldi_step_begin(kh_ctx ctx, kh_mat A, kh_proj proj, kh_mat Md, kh_vec 
                           kh_vec W, int64_t wcol, int64_t k, int64_t start, int sweeps, int gs_mode,
                           double h_km1, int slot);
 int kh_arnoldi_step_end(kh_ctx ctx, int slot, int64_t count, double* hcol_out);
+
+/* One step of Householder Arnoldi (ortho='house': utils.py:970-994, House at utils.py:332-402) in ONE launch (k_house_chain,
+ * krypy_amd/csrc/house.h).  W[:, wcol] holds A v_k (the caller applied the operator; it is not written).  Hv is the
+ * reflector block: column j holds reflector j, zero above row j and normalised (what the reference keeps as House.v);
+ * Beta is a one-column block of at least k + 2 rows that belongs to Hv's owner: Beta[j] = beta_j of reflector j (0 or 2;
+ * the host sets entries of reflectors made elsewhere with kh_vec_set).  The launch applies reflectors 0 .. k to w in
+ * ascending order (beta_j == 0: skipped), makes reflector k + 1 from rows k+1 .. N-1 of the result (written to Hv[:, k+1]
+ * and Beta[k+1]), and stores V[:, k+1] = alpha_{k+1} H_0 ... H_{k+1} e_{k+1}.  _end returns count = k + 6 doubles:
+ *   out[0 .. k]   rows 0 .. k of the reflected w, WITHOUT the factors conj(alpha_j) of utils.py:976 (the caller multiplies:
+ *                 H[j, k] = out[j] * conj(alpha_j); no later reflector reads row j)
+ *   out[k+1 ..]   gamma = w[k+1], sigma^2 = ||w[k+2:]||^2, xnorm (= H[k+1, k]), alpha_{k+1}, beta_{k+1}
+ * Return values beside 0 and the negative kh_status codes: _begin returns KH_HOUSE_NOT_SERVED when this step is not served
+ * by the kernel (kh_ctx_set "house_chain" 0, a communicator, more than 40 double2 rows per lane, k + 1 >= N, k + 2 > 1024, a
+ * refused launch) - real data only: a kh_vec does not know whether it backs a complex block, the caller keeps
+ * complex bases away from this entry (krypy_amd/_hip.py: Context.house_step checks the dtypes) -: nothing was enqueued, the caller applies the reflectors one by one.  _end returns KH_HOUSE_TIMED_OUT
+ * when a grid-wide sum of the launch timed out (or the test switch "chain_fault" faked that): out is not written, column
+ * k + 1 of Hv and V and Beta[k+1] hold garbage, W is intact - the caller re-runs the step on the per-reflector path, which
+ * overwrites all three.  Counters (kh_ctx_get): "n_house_chain" launches, "n_house_recovered" timed-out steps. */
+#define KH_HOUSE_NOT_SERVED 1
+#define KH_HOUSE_TIMED_OUT 2
+int kh_house_step_begin(kh_ctx ctx, kh_vec Hv, kh_vec Beta, kh_vec V, kh_vec W, int64_t wcol, int64_t k, int slot);
+int kh_house_step_end(kh_ctx ctx, int slot, int64_t count, double* out);
 
 /* A run of GMRES iterations in ONE call (krypy/linsys.py:951-997; SURVEY 8b "fused cycle"): Arnoldi steps
  * k0 .. k_stop-1 with look-ahead on the device (kh_arnoldi_step_begin / _end, slots k mod 4), and on the host - in C,

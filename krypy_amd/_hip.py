@@ -104,6 +104,8 @@ _SIGNATURES = {
     "kh_proj_free": [_H],
     "kh_proj_apply_complement": [_H, _H, _H, _I64, _H, _I64, _c_double_p],
     "kh_arnoldi_step_end": [_H, _INT, _I64, _c_double_p],
+    "kh_house_step_begin": [_H, _H, _H, _H, _H, _I64, _I64, _INT],
+    "kh_house_step_end": [_H, _INT, _I64, _c_double_p],
     "kh_residual": [_H, _H, _H, _I64, _H, _I64, _H, _I64, _c_double_p],
     "kh_gmres_cycle": [_H, _H, _H, _H, _H, _H, _I64, _I64, _I64, _INT, _INT, _c_int64_p, _D, _D, _c_double_p, _I64,
                        _c_double_p, _I64, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_int64_p,
@@ -141,6 +143,10 @@ _SIGNATURES = {
     "kh_zproj_create": [_H, _H, _H, _I64, _c_double_p, _c_double_p, _INT, ctypes.POINTER(_H)],
     "kh_zproj_apply_complement": [_H, _H, _H, _I64, _H, _I64, _c_double_p],
 }
+
+# statuses of kh_house_step_begin / _end that are neither success nor an error (krylov_hip.h)
+HOUSE_NOT_SERVED = 1
+HOUSE_TIMED_OUT = 2
 
 _lib = None
 
@@ -842,6 +848,30 @@ class Context(object):
         out = numpy.empty(count, dtype=numpy.complex128 if cplx else numpy.float64)
         _check(self._lib, self._lib.kh_arnoldi_step_end(self._h, slot, count * (2 if cplx else 1),
                                                         _dptr(out)), "kh_arnoldi_step_end")
+        return out
+
+    def house_step(self, Hv, Beta, V, W, wcol, k, slot=0):
+        """One Householder Arnoldi step in one launch (``kh_house_step_begin`` / ``_end``): reflectors ``0 .. k`` of
+        the block ``Hv`` (``Beta[j]``: their factors) are applied to ``W[:, wcol] = A v_k``, reflector ``k+1`` is made
+        and written to ``Hv[:, k+1]`` / ``Beta[k+1]``, and ``V[:, k+1]`` is stored.
+
+        :return: ``k + 6`` numbers - rows ``0 .. k`` of the reflected vector WITHOUT the factors ``conj(alpha_j)``, then
+          ``gamma``, ``sigma^2``, ``xnorm``, ``alpha_{k+1}``, ``beta_{k+1}`` - or ``None`` when the step is not served
+          (complex blocks: checked HERE, the C entry cannot tell; a shape the kernel declines or
+          ``set("house_chain", 0)``: ``KH_HOUSE_NOT_SERVED``; nothing was enqueued), or ``False``
+          when a grid-wide sum of the launch timed out: the caller runs the step on the per-reflector path, ``W`` is
+          untouched."""
+        if not (Hv.dtype == Beta.dtype == V.dtype == W.dtype == _F64):
+            return None
+        rc = self._lib.kh_house_step_begin(self._h, Hv.handle, Beta.handle, V.handle, W.handle, wcol, k, slot)
+        if rc == HOUSE_NOT_SERVED:
+            return None
+        _check(self._lib, rc, "kh_house_step_begin")
+        out = numpy.empty(k + 6, dtype=numpy.float64)
+        rc = self._lib.kh_house_step_end(self._h, slot, k + 6, _dptr(out))
+        if rc == HOUSE_TIMED_OUT:
+            return False
+        _check(self._lib, rc, "kh_house_step_end")
         return out
 
     def residual(self, A, B, bcol, X, xcol, R, rcol):

@@ -85,6 +85,13 @@ struct kh_ctx_s {
     int chain_in_recovery = 0;       // kh_arnoldi_step_end is re-running a step: no re-arming from inside it
     int64_t n_chain_rearmed = 0;     // times the chain family was switched on again (kh_ctx_get "n_chain_rearmed")
     int64_t chain_refused_n = -1;    // vector length whose chain launch the runtime refused (occupancy): that shape only
+    // Householder Arnoldi in one launch (house.h; kh_ctx_set "house_chain"): its own switch and timeout count - a timed-out
+    // launch is re-run by the host layer on the per-reflector path and the next step tries the kernel again; the third
+    // timeout in one context leaves it off
+    int house_chain = 1;
+    int house_recoveries = 0;
+    int64_t n_house_chain = 0, n_house_recovered = 0;
+    int64_t house_refused_n = -1;    // vector length whose launch the runtime refused (occupancy)
     int64_t n_spmm = 0;     // panel applications of a CSR operator that streamed the matrix once
     int chain_spmv = 1;     // banded operators: w = A v_k in the chain kernel's prologue (KRYPY_AMD_CHAIN_SPMV)
     int chain_pf = 1;       // ... and keep HBM busy through the update phase (k_mgs_chain_pf; KRYPY_AMD_CHAIN_PF)

@@ -1669,6 +1669,11 @@ int kh_ctx_set(kh_ctx ctx, const char* key, int64_t value) {
     else if (!strcmp(key, "blk_onex_maxn")) ctx->blk_onex_maxn = value;
     else if (!strcmp(key, "blk_nx")) ctx->blk_nx = value > 0 ? 8 : 0;
     else if (!strcmp(key, "tag_wait")) ctx->tag_wait = value != 0;
+    else if (!strcmp(key, "house_chain")) {
+        ctx->house_chain = value != 0;
+        ctx->house_recoveries = 0;          // (an explicit setting starts the count again)
+        ctx->house_refused_n = -1;
+    }
     else if (!strcmp(key, "chain_epoch")) ctx->chain_epoch = (unsigned)value;      // tests: bring the epoch counter of the grid-wide sums near its wrap
     else if (!strcmp(key, "chain_debug")) ctx->chain_debug = (int)value;    // measurement: phases switched off (garbage results)
     else return fail(KH_ERR_ARG, "kh_ctx_set: unknown key '%s'", key);
@@ -1738,6 +1743,9 @@ int kh_ctx_get(kh_ctx ctx, const char* key, int64_t* value) {
     else if (!strcmp(key, "n_halo_xh")) *value = ctx->n_halo_xh;
     else if (!strcmp(key, "n_allreduce")) *value = ctx->n_allreduce;
     else if (!strcmp(key, "n_chain_recovered")) *value = ctx->n_chain_recovered;
+    else if (!strcmp(key, "house_chain")) *value = ctx->house_chain;
+    else if (!strcmp(key, "n_house_chain")) *value = ctx->n_house_chain;
+    else if (!strcmp(key, "n_house_recovered")) *value = ctx->n_house_recovered;
     else if (!strcmp(key, "chain_epoch")) *value = ctx->chain_epoch;
     else if (!strcmp(key, "n_epoch_wraps")) *value = ctx->n_epoch_wraps;
     else return fail(KH_ERR_ARG, "kh_ctx_get: unknown key '%s'", key);
@@ -2162,6 +2170,35 @@ int dia_rebuild_for_halo(kh_ctx ctx, kh_mat A) {
     }
     return 0;
 }
+// The host's wait for an H-column slot (kh_arnoldi_step_end, kh_house_step_end): the completion tag the step's last kernel
+// writes behind the pinned column (CH_SIGNAL_DONE), or - steps whose last kernel writes none - the slot's event.  Should
+// the tag never show up the stream running empty says the same thing later.
+int wait_slot(kh_ctx ctx, int slot) {
+    if (!ctx->wait_tag[slot]) {
+        KH_HIP(hipEventSynchronize(ctx->hev[slot]));
+        return 0;
+    }
+    volatile int* tagp = ctx->done_pin[slot];
+    const int want = ctx->done_seq[slot];
+    for (unsigned spins = 1; *tagp != want; ++spins) {
+#if defined(__x86_64__) || defined(__i386__)
+        __builtin_ia32_pause();
+#endif
+        if ((spins & 0x3fffu) == 0) {
+            const hipError_t q = hipStreamQuery(ctx->stream);
+            if (q == hipSuccess) break;
+            if (q != hipErrorNotReady) {          // a sticky launch / device error: the tag will never come
+                ctx->wait_tag[slot] = false;
+                KH_HIP(q);
+            }
+        }
+    }
+    __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    ctx->wait_tag[slot] = false;
+    ctx->n_tag_waits += 1;
+    return 0;
+}
+
 }  // namespace kh
 }  // extern "C++"
 
@@ -3065,30 +3102,7 @@ int kh_arnoldi_step_end(kh_ctx ctx, int slot, int64_t count, double* hcol_out) {
     KH_ARG(slot >= 0 && slot < KH_NSLOT && count >= 0 && count <= ctx->hcap,
            "kh_arnoldi_step_end: slot %d / count %lld", slot, (long long)count);
     KH_ARG(ctx->hev[slot] != nullptr, "kh_arnoldi_step_end: no step was begun");
-    if (ctx->wait_tag[slot]) {
-        // the step's chain kernel writes its tag behind the H column (CH_SIGNAL_DONE).  Should the tag never show up
-        // the stream running empty says the same thing later.
-        volatile int* tagp = ctx->done_pin[slot];
-        const int want = ctx->done_seq[slot];
-        for (unsigned spins = 1; *tagp != want; ++spins) {
-#if defined(__x86_64__) || defined(__i386__)
-            __builtin_ia32_pause();
-#endif
-            if ((spins & 0x3fffu) == 0) {
-                const hipError_t q = hipStreamQuery(ctx->stream);
-                if (q == hipSuccess) break;
-                if (q != hipErrorNotReady) {          // a sticky launch / device error: the tag will never come
-                    ctx->wait_tag[slot] = false;
-                    KH_HIP(q);
-                }
-            }
-        }
-        __atomic_thread_fence(__ATOMIC_ACQUIRE);
-        ctx->wait_tag[slot] = false;
-        ctx->n_tag_waits += 1;
-    } else {
-        KH_HIP(hipEventSynchronize(ctx->hev[slot]));
-    }
+    KH_TRY(wait_slot(ctx, slot));
     KH_TRY(xr_check(ctx));
     // the one-launch projector of a deflated step (proj_reg.h) reports a timed-out sum in a word of its own: the step - its w
     // was garbage whatever Gram-Schmidt kernels followed - is re-run below with the four-launch projector, the kernel stays

@@ -47,6 +47,7 @@ int grid_for(kh_ctx ctx, int64_t n);
 int grid_lin(kh_ctx ctx, int64_t n);
 double* part_slot(kh_ctx ctx, int slot);          // partial-sum slots inside ctx->part
 int ensure_hcap(kh_ctx ctx, int64_t need);
+int wait_slot(kh_ctx ctx, int slot);      // completion tag or event of an H-column slot (krylov_hip.hip)
 int check_vec(kh_vec v, int64_t col, int64_t ncols, const char* what);
 int fetch_scalars(kh_ctx ctx, const double* dev, int64_t count, double* out);
 int push_scalars(kh_ctx ctx, const double* host, int64_t count, double* dev);

@@ -453,6 +453,16 @@ class _DevHouse(object):
         self.ctx.axpy_panel(self.Hv, self.j, 1, [self.beta * d], X, xcol)
 
 
+class _FusedHouse(_DevHouse):
+    """Reflector ``j`` as the one-launch step left it (``Context.house_step``): column ``j`` of the reflector block holds
+    the same representation :class:`_DevHouse` builds, the scalars came back with the H column - nothing is computed
+    here, and :meth:`apply` is the inherited per-reflector one (a step taken on that path after this one uses it)."""
+
+    def __init__(self, ctx, Hv, j, alpha, beta, xnorm):
+        self.ctx, self.Hv, self.j = ctx, Hv, j
+        self.alpha, self.beta, self.xnorm = float(alpha), float(beta), float(xnorm)
+
+
 # ----------------------------------------------------------------------------------------
 # Givens rotation (utils.py:405-436) - host, O(1)
 # ----------------------------------------------------------------------------------------
@@ -1042,9 +1052,10 @@ class Arnoldi(object):
         :param A: linear operator (anything :func:`get_linearoperator` accepts).
         :param v: initial vector, ``(N,1)`` ndarray (or a :class:`DVec`).
         :param maxiter: maximal number of iterations (default ``N``).
-        :param ortho: ``'mgs'`` (default), ``'dmgs'``, ``'lanczos'`` as in the reference
-            (``'house'`` is a sequential reflector chain, out of scope of the device path), plus
-            the extensions ``'cgs'`` / ``'cgs2'`` (panel Gram-Schmidt, one / two passes).
+        :param ortho: ``'mgs'`` (default), ``'dmgs'``, ``'lanczos'``, ``'house'`` as in the reference
+            (``'house'``: real data on one GPU takes one launch per step, ``k_house_chain``; everything
+            else applies the reflectors one by one), plus the extensions ``'cgs'`` / ``'cgs2'`` (panel
+            Gram-Schmidt, one / two passes).
         :param M: self-adjoint positive definite preconditioner; then ``P`` with ``V = M P``
             is built too.
         :param ip_B: inner product, see :func:`inner`.
@@ -1159,10 +1170,16 @@ class Arnoldi(object):
         self._enq = 0          # number of steps enqueued on the device so far
         if ortho == "house":
             # Householder Arnoldi (utils.py:910-922, 970-994): reflectors live zero-padded in their
-            # own (N, maxiter+2) block; every application is a device dot + axpy.  Sequential by
-            # nature (SURVEY: not a hot path), kept for its orthogonality guarantee.
+            # own (N, maxiter+2) block.  Sequential like modified Gram-Schmidt, and run the same way: a
+            # context that offers `house_step` applies all reflectors of a step, makes the new one and
+            # builds v_{k+1} in ONE launch (csrc/house.h) with the factors beta_j in a device array of
+            # this object's; steps it declines (complex data, N ranks, long vectors) and contexts
+            # without it apply every reflector as a device dot + axpy (_advance_house).
             self._fused, self._lookahead = False, 0
             self._Hv = ctx.alloc(N, min(self.maxiter + 1, N) + 1, dtype=bdt)
+            self._Hbeta = None
+            if getattr(ctx, "house_step", None) is not None and not cplx:
+                self._Hbeta = ctx.alloc(self._Hv.ncols, 1, dtype=bdt)
 
         # A preconditioner that is NOT a device matrix (a callable such as an incomplete-factorisation solve, a
         # composite operator): the Gram-Schmidt part of the step does not depend on M at all - coefficients against
@@ -1178,6 +1195,7 @@ class Arnoldi(object):
         v = _as_dvec(v, ctx, dtype=bdt)
         if ortho == "house":
             self.houses = [_DevHouse(ctx, self._Hv, 0, v.block, v.col)]
+            self._put_beta(0)
             self.vnorm = norm(v)
         elif self.M is not None:
             p = v
@@ -1431,10 +1449,31 @@ class Arnoldi(object):
             if self._BV is not None:
                 self._BV.zero(k + 1 - self._base, 1)      # (0 / 0: nothing non-finite goes back to the block pool)
 
+    def _put_beta(self, j):
+        """Reflector ``j`` was made on the per-reflector path: the one-launch step reads its factor from the device."""
+        if self._Hbeta is not None:
+            self._Hbeta.set(0, j, [float(self.houses[j].beta)])
+
     def _advance_house(self, k):
         """One Householder Arnoldi step (utils.py:970-994) on the device."""
         ctx, V, W, H, N = self._ctx, self._V, self._W, self.H, self._V.n
         self.A._apply_dev(V, k, W, 0, 1)
+        step = getattr(ctx, "house_step", None) if self._Hbeta is not None else None
+        if step is not None:
+            # one launch, one host wait.  Rows 0 .. k come back without the factors conj(alpha_j) (no later reflector
+            # reads row j: applied here), H[k+1, k] is the new reflector's xnorm, its scalars come along.  None: the
+            # step is not served; False: a sum of the launch timed out - A v_k is untouched, the code below re-runs
+            # the step and overwrites column k+1 of both blocks and beta[k+1].
+            self._claim(0)
+            out = step(self._Hv, self._Hbeta, V, W, 0, k)
+            self._release(0)
+            if out is not None and out is not False:
+                alphas = numpy.array([h.alpha for h in self.houses[: k + 1]])
+                H[: k + 1, k] = out[: k + 1] * numpy.conj(alphas)
+                xnorm, alpha, beta = out[k + 3], out[k + 4], out[k + 5]
+                H[k + 1, k] = xnorm
+                self.houses.append(_FusedHouse(ctx, self._Hv, k + 1, alpha, beta, xnorm))
+                return float(xnorm)
         for j in range(k + 1):
             hj = self.houses[j]
             hj.apply(W, 0)
@@ -1443,6 +1482,7 @@ class Arnoldi(object):
         if k + 1 < N:
             house = _DevHouse(ctx, self._Hv, k + 1, W, 0)
             self.houses.append(house)
+            self._put_beta(k + 1)
             house.apply(W, 0)
             col = W.get(0, 0, k + 2)
             col[k + 1] *= numpy.conj(house.alpha)
