@@ -1880,7 +1880,17 @@ int kh_vec_download(kh_vec v, int64_t col0, int64_t ncols, double* host, int64_t
 
 int kh_vec_zero(kh_vec v, int64_t col0, int64_t ncols) {
     KH_TRY(check_vec(v, col0, ncols, "kh_vec_zero"));
-    chain_blk_touch(v->ctx, v);
+    // Row j of the blocked kernels' Gram table is made of columns <= j only: clearing columns >= col0 leaves rows < col0
+    // what they were.  A discarded look-ahead step (utils.Arnoldi._settle clears the column it wrote) therefore hands the
+    // table back as the step before it left it, and the step that is begun again finds the rows its first launch found -
+    // the sequence keeps the bits of an undisturbed one instead of going on with rows rebuilt from the basis, which round
+    // differently.  Every other write to the block withdraws the whole table (chain_blk_touch), as does this one for the
+    // one-reduction form's table.
+    {
+        const int64_t keep = (v->ctx->blk_V == v && v->ctx->blk_next >= col0) ? col0 - 1 : v->ctx->blk_next;
+        chain_blk_touch(v->ctx, v);
+        if (v->ctx->blk_V == v) v->ctx->blk_next = keep;
+    }
     if (ncols == 0) return 0;
     KH_HIP(hipMemsetAsync(v->col(col0), 0, sizeof(double) * v->ld * ncols, v->ctx->stream));
     return 0;

@@ -454,6 +454,68 @@ def shard_round(ctx, seed):
     return checks
 
 
+def house_round(ctx, seed):
+    """kh_house_step_begin / _end (the one-launch Householder Arnoldi step) on constructed state: random length, step, pattern
+    of zero factors, column of W and slot, against the extended-precision step of tests/support/house_ref.py through the
+    comparison of tests/test_gpu_house_step.py (bar: 16 x the error of a float64 NumPy run of the same step, or
+    16 eps sqrt(k + 2)), and what the call must leave alone, bit for bit.  A context without the entry, or one that declines
+    (a communicator), contributes nothing."""
+    if not hasattr(ctx, "house_step"):
+        return 0
+    from tests.support.house_ref import Step, assert_step_matches, house_step_longdouble, reflector_state
+    rng = np.random.default_rng(210_000 + seed)
+    n = max(2, pick_n(rng, 300_000))
+    k = int(rng.integers(0, min(n - 1, 40)))
+    if n <= 20_000 and rng.integers(0, 4) == 0:           # now and then a deep step: wave boundaries of the row owners
+        k = min(n - 2, int(rng.choice([62, 63, 126, 127, 128, 255, 511, 1022])))
+    p_zero = float(rng.choice([0.0, 0.2, 0.5, 1.0]))
+    zero = [j for j in range(k + 1) if rng.random() < p_zero]
+    wcol, slot = int(rng.integers(0, 3)), int(rng.integers(0, 4))
+    st = reflector_state(n, k + 1, 210_000 + seed, zero)
+    U = st.block(0, k + 1)
+    cols = lambda j: U[:, j]            # noqa: E731
+    for attempt in range(6):            # |gamma| well away from zero: the sign branch must not hang on rounding
+        W = rng.standard_normal((n, 3))
+        ref = house_step_longdouble(cols, st.beta, W[:, wcol], k)
+        wnorm = float(np.linalg.norm(W[:, wcol]))
+        if abs(float(ref.gamma)) >= 1e-6 * wnorm:
+            break
+    else:
+        raise AssertionError("seed %d: no w with |gamma| >= 1e-6 ||w||" % seed)
+    yard = house_step_longdouble(cols, st.beta, W[:, wcol], k, dtype=np.float64)
+    sentinel, junk = rng.standard_normal(n), np.full(n, -3.25)
+    Hv, V = ctx.alloc(n, k + 3), ctx.alloc(n, k + 3)
+    Beta, Wd = ctx.alloc(k + 3, 1), ctx.upload(W)
+    Hv.upload(0, U)
+    Hv.upload(k + 1, junk)
+    Hv.upload(k + 2, sentinel)
+    V.upload(0, np.tile(sentinel.reshape(-1, 1), (1, k + 3)))
+    b = np.r_[st.beta, -3.25, 0.125]
+    Beta.upload(0, b)
+    out = ctx.house_step(Hv, Beta, V, Wd, wcol, k, slot)
+    if out is None:
+        return 0
+    what = "seed %d (n=%d, k=%d, %d zero factors, wcol=%d, slot=%d)" % (seed, n, k, len(zero), wcol, slot)
+    if out is False:
+        raise AssertionError(what + ": a grid-wide sum timed out")
+    Hd, Vd, bd = Hv.download(), V.download(), Beta.download()[:, 0]
+    got = Step(out[: k + 1], out[k + 1], out[k + 2], out[k + 3], out[k + 4], out[k + 5], Hd[:, k + 1], Vd[:, k + 1])
+    try:
+        assert_step_matches(got, ref, yard, k, wnorm)
+    except AssertionError as e:
+        raise AssertionError("%s: %s" % (what, e))
+    keep = [c for c in range(k + 3) if c != k + 1]
+    same = (np.array_equal(Hd[:, : k + 1], U) and np.array_equal(Hd[:, k + 2], sentinel)
+            and np.array_equal(Vd[:, keep], np.tile(sentinel.reshape(-1, 1), (1, k + 2)))
+            and np.array_equal(Wd.download(), W) and np.array_equal(bd[[j for j in range(k + 3) if j != k + 1]], b[keep])
+            and bd[k + 1] == float(ref.beta))
+    if not same:
+        raise AssertionError(what + ": the step changed something besides column k + 1 of the two blocks and beta[k + 1]")
+    if Hv.padding_nonzero() or V.padding_nonzero() or Beta.padding_nonzero():
+        raise AssertionError(what + ": padding written")
+    return 8 + 6
+
+
 if __name__ == "__main__":
     rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 60
     max_n = int(sys.argv[2]) if len(sys.argv) > 2 else 300000
@@ -473,4 +535,5 @@ if __name__ == "__main__":
         total += shard_round(ctx, seed)
         total += cycle_round(ctx, dbl, seed)
         total += minres_cycle_round(ctx, dbl, seed)
+        total += house_round(ctx, seed)
     print("abi_fuzz: %d rounds, %d comparisons, all within tolerance" % (rounds, total))
