@@ -1014,14 +1014,18 @@ __global__ __launch_bounds__(CH_BS) void k_mgs_chain(ChainArgs a) {
 //
 // A link reads its column twice - v_j for the dot, then (without a preconditioner) the same v_j for
 // the update, after the grid-wide reduction.  The workgroup owns a whole CU (512 threads, 160 KB of
-// LDS, ~4 KB used), so the first LB batches of the column (LB*PB rows x 512 lanes x 16 B = up to
-// 128 KB) are copied into LDS while the dot phase streams them and the update phase takes them from
+// LDS, ~4 KB used), so the first LROWS rows of the column (LROWS x 512 lanes x 16 B = up to
+// 152 KB) are copied into LDS while the dot phase streams them and the update phase takes them from
 // there.  The update phase also walks the batches in REVERSE order, so the last batch of the dot phase
-// is still in the register ring and is used again without any load.  At N = 10^7 (R2 = 40, batches
-// of 5 rows): 15 rows from LDS + 5 from the ring = half of the second read, 25 % less HBM traffic per
-// link; for R2 <= 16 the second read disappears altogether.  Only for B == V (no preconditioner).
-// Ring parity: batch NB-1 sits in ring[1]; the NG = NB - LB - 1 batches that still come from memory
-// start in ring[0] and NG is even, so the next column's first batch lands in ring[0] again.
+// is still in the register ring and is used again without any load.  The parked set is a ROW count
+// (LROWS): at N = 10^7 (R2 = 40, batches of 5 rows) it is 19 rows - three whole batches and four rows
+// of the fourth, all the LDS there is beside smd / smu / slead - so 19 rows from LDS + 5 from the ring
+// = 24 of the 40 rows of the second read stay on the chip and 16 rows (4 MB per XCD, the size of its
+// L2) are read again; the split batch parks rows 15..18 in the dot phase and re-reads row 19 alone.
+// For R2 <= 16 the second read disappears altogether.  Only for B == V (no preconditioner).
+// Ring parity: batch NB-1 sits in ring[1]; the NG = NB - 1 - LROWS / PB ring steps that bring rows back
+// from memory start in ring[0] and NG is even, so the next column's first batch lands in ring[0] again
+// (the step of a split batch loads only its rows >= LROWS).
 // ------------------------------------------------------------------------------------------
 // (experiment knob: the first KH_CH_REUSE_SKIP of the batches that come back from memory for the update are
 // streamed non-temporally as well, i.e. given up to HBM so that the others fit the 4 MB of L2 per XCD)
@@ -1043,14 +1047,23 @@ struct ChainShapeLds {
     // with it and is still 14 % faster than the plain kernel; 4-row batches spill 42)
     static constexpr int PB = ChainShape<R2>::PB;
     static constexpr int NB = R2 / PB;
-    static constexpr int LB = NB >= 4 ? 3 : 1;                // leading batches kept in LDS
-    static constexpr int NG = NB - LB - 1;                    // update batches that still come from memory
-    static_assert((NB % 2) == 0 && NG >= 0 && (NG % 2) == 0, "ring parity must reset every phase");
-    // R2 = 40 fills the register file to the last VGPR (w alone takes 160 of the 256); the 36 KB of LDS the parked
-    // batches leave free take the last WL = 4 rows of w instead (k_mgs_chain's W_GET / W_PUT): 16 registers back,
-    // no scratch traffic in the link loop (18 spilled registers with the operator in the prologue otherwise)
+    // R2 = 40 fills the register file to the last VGPR (w alone takes 160 of the 256) and the pressure peaks in the
+    // operator prologue, where four rows of gathers are in flight beside w (18 spilled registers otherwise).  So
+    // the PROLOGUE (the operator's Put and the presub loop) keeps the last WL = 4 rows of w in LDS; they move into
+    // w[R2 - WL ...] before the first ring load, and the link loop, the norm and the store have all of w in
+    // registers.  The LDS entries are the lane's own (no barrier) and lie inside the parked rows, which are first
+    // written by the first link's dot phase: the two users of that LDS are never live at the same time.
     static constexpr int WL = (R2 == 40 && !CPLX) ? 4 : 0;
-    static constexpr size_t LDS_BYTES = (size_t)(LB * PB + WL) * CH_BS * sizeof(double2);
+    // rows parked in LDS: three whole batches (one for the short shapes); R2 = 40 real takes what 160 KB hold
+    // beside the static arrays, 19 rows = 152 KB (20 would leave no room for smd / smu / slead)
+    static constexpr int LROWS = (R2 == 40 && !CPLX) ? 19 : (NB >= 4 ? 3 : 1) * PB;
+    static constexpr int NG = NB - 1 - LROWS / PB;            // ring steps of the update that load rows from memory
+    static_assert((NB % 2) == 0 && NG >= 0 && (NG % 2) == 0, "ring parity must reset every phase");
+    static_assert(WL <= LROWS && LROWS <= R2 - PB, "the prologue's rows of w borrow parked rows; the last batch stays in the ring");
+    static constexpr size_t LDS_BYTES = (size_t)LROWS * CH_BS * sizeof(double2);
+    // static LDS of k_mgs_chain_lds: smd[4 * CH_BS / 64] doubles, smu[2 * CH_GMAX] words, slead
+    static constexpr size_t STATIC_LDS = 4 * (CH_BS / 64) * sizeof(double) + 2 * CH_GMAX * sizeof(unsigned) + sizeof(int);
+    static_assert(LDS_BYTES + STATIC_LDS <= 160 * 1024, "a CU has 160 KB of LDS");
 };
 
 template <int R2, bool MASKED, bool CPLX = false, int FND = 0, bool XR = false>
@@ -1059,18 +1072,23 @@ __global__ __launch_bounds__(CH_BS) void k_mgs_chain_lds(ChainArgs a) {
     static_assert(!XR || !CPLX, "the cross-rank stage exists for real vectors");
     constexpr int PB = ChainShapeLds<R2, CPLX>::PB;
     constexpr int NB = ChainShapeLds<R2, CPLX>::NB;
-    constexpr int LB = ChainShapeLds<R2, CPLX>::LB;
+    constexpr int LROWS = ChainShapeLds<R2, CPLX>::LROWS;
+    constexpr int LBC = (LROWS + PB - 1) / PB;    // batches with a parked row
+    constexpr bool SPLIT = (LROWS % PB) != 0;     // the last of them is parked in part (the row tests below fold away otherwise)
     constexpr int NG = ChainShapeLds<R2, CPLX>::NG;
-    constexpr int WL = ChainShapeLds<R2, CPLX>::WL;
-    constexpr int RW = R2 - WL;                   // rows of w in registers
-    extern __shared__ __attribute__((aligned(16))) double2 vlds[];   // [LB*PB parked rows + WL rows of w][CH_BS]
-    double2* const wl = vlds + (size_t)LB * PB * CH_BS;
-#define W_GET(r) (((r) < RW) ? w[((r) < RW) ? (r) : 0] : wl[((r) - RW) * CH_BS + tid])
-#define W_PUT(r, val)                                   \
-    do {                                                \
-        if ((r) < RW) w[((r) < RW) ? (r) : 0] = (val);  \
-        else wl[((r) - RW) * CH_BS + tid] = (val);      \
+    // prologue only: the operator's last WL rows of w wait in LDS (the FND = 0 prologue loads straight into registers)
+    constexpr int WL = FND > 0 ? ChainShapeLds<R2, CPLX>::WL : 0;
+    constexpr int RW = R2 - WL;                   // rows of w the prologue holds in registers
+    extern __shared__ __attribute__((aligned(16))) double2 vlds[];   // [LROWS parked rows][CH_BS]; the first WL: the prologue's rows of w
+    // row r of w with the first NR rows in registers
+#define W_GET_N(r, NR) (((r) < (NR)) ? w[((r) < (NR)) ? (r) : 0] : vlds[((r) - (NR)) * CH_BS + tid])
+#define W_PUT_N(r, val, NR)                                 \
+    do {                                                    \
+        if ((r) < (NR)) w[((r) < (NR)) ? (r) : 0] = (val);  \
+        else vlds[((r) - (NR)) * CH_BS + tid] = (val);      \
     } while (0)
+#define W_GET(r) W_GET_N(r, RW)
+#define W_PUT(r, val) W_PUT_N(r, val, RW)
     __shared__ double smd[4 * (CH_BS / 64)];
     __shared__ unsigned smu[2 * CH_GMAX];
     __shared__ int slead;
@@ -1085,7 +1103,7 @@ __global__ __launch_bounds__(CH_BS) void k_mgs_chain_lds(ChainArgs a) {
     // keeps it; everything that is used once (the batches that live on in LDS / the ring, the second
     // read itself, w) is loaded non-temporally and does not evict it
 #define CH_LD(ptr, reuse) ((reuse) ? *(ptr) : ld_nt2(ptr))
-    double2 w[RW];
+    double2 w[R2];
     double2 ring[2][PB];
     if constexpr (FND > 0 && CPLX) {
         chain_apply_banded_z<R2, FND>(a, first, [&](int r, double s0, double s1) { W_PUT(r, make_double2(s0, s1)); });
@@ -1116,6 +1134,17 @@ __global__ __launch_bounds__(CH_BS) void k_mgs_chain_lds(ChainArgs a) {
             if ((r + 1) % 8 == 0) CH_ISSUE_FENCE();
         }
     }
+    // the prologue's registers are dead: all of w lives in registers from here on (own LDS entries: program order is enough)
+    if constexpr (WL > 0) {
+#pragma unroll
+        for (int r = RW; r < R2; ++r) w[r] = vlds[(r - RW) * CH_BS + tid];
+        CH_ISSUE_FENCE();
+    }
+    // (the same accessor with all R2 rows in registers: written as a plain w[r] the masked instantiations take 30 more registers)
+#undef W_PUT
+#undef W_GET
+#define W_GET(r) W_GET_N(r, R2)
+#define W_PUT(r, val) W_PUT_N(r, val, R2)
     unsigned epoch = a.epoch0;
     if (a.debug == 4 && tid == 0) __hip_atomic_store(a.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // tests: a faked timeout
     const int total = a.ncol * a.sweeps;
@@ -1135,24 +1164,27 @@ __global__ __launch_bounds__(CH_BS) void k_mgs_chain_lds(ChainArgs a) {
         const double2* __restrict__ vn = (t + 1 < total)
             ? reinterpret_cast<const double2*>(a.V + jn * a.ld) + first
             : reinterpret_cast<const double2*>(a.w_in) + first;       // harmless: valid memory
-        // ---- dot phase: <v_j, w>; the first LB batches are parked in LDS on the way ----
+        // ---- dot phase: <v_j, w>; the first LROWS rows are parked in LDS on the way ----
         double acc0 = 0.0, acc1 = 0.0;
         CH_STAMP(a, t, total, 0);
 #pragma unroll
         for (int b = 0; b < NB; ++b) {
-            // next: v_j batch b+1; after the last one the first update batch that is not in LDS
-            // (or, if the whole column is, the next column's first batch)
+            // next: v_j batch b+1; after the last one the first update batch that is not in LDS (of a split batch
+            // only the rows that are not) or, if the whole column is, the next column's first batch
             const double2* __restrict__ nx = (b + 1 < NB) ? v2 + (int64_t)(b + 1) * PB * CH_BS
                                                             : (NG > 0 ? v2 + (int64_t)(NB - 2) * PB * CH_BS : vn);
 #pragma unroll
-            for (int i = 0; i < PB; ++i)
-                ring[(b + 1) & 1][i] = CH_LD(nx + (int64_t)i * CH_BS, (b + 1 < NB) && (b + 1 >= LB + KH_CH_REUSE_SKIP) && (b + 1 <= NB - 2 - KH_CH_SKIP_LAST));
+            for (int i = 0; i < PB; ++i) {
+                if (!SPLIT || b + 1 < NB || NG == 0 || (NB - 2) * PB + i >= LROWS)
+                    ring[(b + 1) & 1][i] = CH_LD(nx + (int64_t)i * CH_BS, (b + 1 < NB) && (!SPLIT || (b + 1) * PB + i >= LROWS) &&
+                                                                              (b + 1 >= LROWS / PB + KH_CH_REUSE_SKIP) && (b + 1 <= NB - 2 - KH_CH_SKIP_LAST));
+            }
             CH_ISSUE_FENCE();
 #pragma unroll
             for (int i = 0; i < PB; ++i) {
                 double2 v = ring[b & 1][i];
                 if (MASKED && !CH_OK(b * PB + i)) v = make_double2(0.0, 0.0);   // beyond the vector: whatever the block holds there
-                if (b < LB) vlds[(b * PB + i) * CH_BS + tid] = v;
+                if (SPLIT ? (b * PB + i < LROWS) : (b < LBC)) vlds[(b * PB + i) * CH_BS + tid] = v;
                 const double2 wr = W_GET(b * PB + i);
                 if (CPLX) {
                     acc0 = fma(v.x, wr.x, acc0);
@@ -1210,42 +1242,50 @@ __global__ __launch_bounds__(CH_BS) void k_mgs_chain_lds(ChainArgs a) {
         // (a) the last batch of the dot phase is still in ring[1]
 #pragma unroll
         for (int i = 0; i < PB; ++i) CH_UPD((NB - 1) * PB + i, ring[1][i]);
-        // (b) batches NB-2 ... LB from memory through the ring
+        // (b) rows (NB-1)*PB - 1 ... LROWS from memory through the ring, a batch per step (the last step may be a part of one)
         constexpr bool EARLY = (KH_CH_LDS_EARLY != 0) && NG >= 2;
 #pragma unroll
         for (int g = 0; g < NG; ++g) {
             const int b = NB - 2 - g;
             const double2* __restrict__ nx = (g + 1 < NG) ? v2 + (int64_t)(b - 1) * PB * CH_BS : vn;
 #pragma unroll
-            for (int i = 0; i < PB; ++i) ring[(g + 1) & 1][i] = CH_LD(nx + (int64_t)i * CH_BS, false);
+            for (int i = 0; i < PB; ++i) {
+                if (!SPLIT || g + 1 == NG || (b - 1) * PB + i >= LROWS) ring[(g + 1) & 1][i] = CH_LD(nx + (int64_t)i * CH_BS, false);
+            }
             CH_ISSUE_FENCE();
             if (EARLY && g == 1) {
                 // two re-read batches are in flight (this iteration's load and the previous one's): walk the
                 // LDS-parked head of the column while they are on their way
 #pragma unroll
-                for (int bb = LB - 1; bb >= 0; --bb) {
+                for (int bb = LBC - 1; bb >= 0; --bb) {
 #pragma unroll
                     for (int i = 0; i < PB; ++i) {
-                        const double2 p = vlds[(bb * PB + i) * CH_BS + tid];
-                        CH_UPD(bb * PB + i, p);
+                        if (!SPLIT || bb * PB + i < LROWS) {
+                            const double2 p = vlds[(bb * PB + i) * CH_BS + tid];
+                            CH_UPD(bb * PB + i, p);
+                        }
                     }
                     CH_ISSUE_FENCE();
                 }
             }
 #pragma unroll
-            for (int i = 0; i < PB; ++i) CH_UPD(b * PB + i, ring[g & 1][i]);
+            for (int i = 0; i < PB; ++i) {
+                if (!SPLIT || b * PB + i >= LROWS) CH_UPD(b * PB + i, ring[g & 1][i]);
+            }
         }
         CH_STAMP(a, t, total, 6);
         // (c) the head of the column from LDS (own entries: no barrier needed), one batch of reads at
         //     a time (hoisted all together they would spill)
         if (!EARLY) {
 #pragma unroll
-            for (int b = LB - 1; b >= 0; --b) {
+            for (int b = LBC - 1; b >= 0; --b) {
                 CH_ISSUE_FENCE();
 #pragma unroll
                 for (int i = 0; i < PB; ++i) {
-                    const double2 p = vlds[(b * PB + i) * CH_BS + tid];
-                    CH_UPD(b * PB + i, p);
+                    if (!SPLIT || b * PB + i < LROWS) {
+                        const double2 p = vlds[(b * PB + i) * CH_BS + tid];
+                        CH_UPD(b * PB + i, p);
+                    }
                 }
             }
         }
@@ -1321,6 +1361,8 @@ __global__ __launch_bounds__(CH_BS) void k_mgs_chain_lds(ChainArgs a) {
     }
 #undef W_PUT
 #undef W_GET
+#undef W_PUT_N
+#undef W_GET_N
 #undef CH_LD
 #undef CH_OK
 }
