@@ -284,6 +284,20 @@ int kh_arnoldi_step_end(kh_ctx ctx, int slot, int64_t count, double* hcol_out);
 int kh_house_step_begin(kh_ctx ctx, kh_vec Hv, kh_vec Beta, kh_vec V, kh_vec W, int64_t wcol, int64_t k, int slot);
 int kh_house_step_end(kh_ctx ctx, int slot, int64_t count, double* out);
 
+/* The same step for complex (c128) data (utils.py:970-994 with a complex basis; House at utils.py:332-402, the scalar
+ * branches at 349-377 with a complex gamma) in ONE launch (k_zhouse_chain, krypy_amd/csrc/house.h).  Hv, V and W are the
+ * (re, im) views of complex blocks (length 2 N), Beta is a plain f64 vector as above: the factors are real.  The links are
+ * d = conj(u_j) . w, w -= (beta_j d) u_j; reflector k + 1 has v0 = gamma + gamma / |gamma| xnorm, alpha = -gamma / |gamma|.
+ * _end returns count = 2 (k + 1) + 7 doubles:
+ *   out[0 .. 2k+1]   rows 0 .. k of the reflected w as (re, im) pairs, WITHOUT the factors conj(alpha_j)
+ *   out[2k+2 ..]     Re gamma, Im gamma, sigma^2, xnorm (= H[k+1, k]), Re alpha_{k+1}, Im alpha_{k+1}, beta_{k+1}
+ * KH_HOUSE_NOT_SERVED from _begin: kh_ctx_set "house_chain" 0, a spent recovery budget (three timed-out launches, shared
+ * with the real step), a communicator, more than 32 double2 rows per lane (N > 32 * 512 * compute units complex rows:
+ * 4,194,304 on 256 CUs - the 40-row class of the real step is not served here), k + 1 >= N, k + 2 > 1024, a refused launch.  KH_HOUSE_TIMED_OUT from _end as above.  Counter: "n_zhouse_chain" launches
+ * ("n_house_chain" counts the real step only); "n_house_recovered" is shared. */
+int kh_zhouse_step_begin(kh_ctx ctx, kh_vec Hv, kh_vec Beta, kh_vec V, kh_vec W, int64_t wcol, int64_t k, int slot);
+int kh_zhouse_step_end(kh_ctx ctx, int slot, int64_t count, double* out);
+
 /* A run of GMRES iterations in ONE call (krypy/linsys.py:951-997; SURVEY 8b "fused cycle"): Arnoldi steps
  * k0 .. k_stop-1 with look-ahead on the device (kh_arnoldi_step_begin / _end, slots k mod 4), and on the host - in C,
  * not in the caller's interpreter - what the reference does between two steps: the new Hessenberg column through the

@@ -106,6 +106,8 @@ _SIGNATURES = {
     "kh_arnoldi_step_end": [_H, _INT, _I64, _c_double_p],
     "kh_house_step_begin": [_H, _H, _H, _H, _H, _I64, _I64, _INT],
     "kh_house_step_end": [_H, _INT, _I64, _c_double_p],
+    "kh_zhouse_step_begin": [_H, _H, _H, _H, _H, _I64, _I64, _INT],
+    "kh_zhouse_step_end": [_H, _INT, _I64, _c_double_p],
     "kh_residual": [_H, _H, _H, _I64, _H, _I64, _H, _I64, _c_double_p],
     "kh_gmres_cycle": [_H, _H, _H, _H, _H, _H, _I64, _I64, _I64, _INT, _INT, _c_int64_p, _D, _D, _c_double_p, _I64,
                        _c_double_p, _I64, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_int64_p,
@@ -872,6 +874,33 @@ class Context(object):
         if rc == HOUSE_TIMED_OUT:
             return False
         _check(self._lib, rc, "kh_house_step_end")
+        return out
+
+    def zhouse_step(self, Hv, Beta, V, W, wcol, k, slot=0):
+        """:meth:`house_step` for complex (c128) blocks (``kh_zhouse_step_begin`` / ``_end``, ``k_zhouse_chain``): ``Hv``,
+        ``V``, ``W`` are complex, ``Beta`` is a real (f64) block - the factors are 0 or 2.  The links are
+        ``d = conj(u_j) . w``, ``w -= (beta_j d) u_j``.
+
+        :return: a complex array of ``k + 6`` numbers - rows ``0 .. k`` of the reflected vector WITHOUT the factors
+          ``conj(alpha_j)``, then ``gamma``, ``sigma^2``, ``xnorm``, ``alpha_{k+1}``, ``beta_{k+1}`` (the real ones with
+          a zero imaginary part) - or ``None`` when the step is not served (other dtypes: checked HERE; a shape the kernel
+          declines or ``set("house_chain", 0)``: nothing was enqueued), or ``False`` when a grid-wide sum of the launch
+          timed out: the caller runs the step on the per-reflector path, ``W`` is untouched."""
+        if not (Hv.dtype == V.dtype == W.dtype == _C128 and Beta.dtype == _F64):
+            return None
+        rc = self._lib.kh_zhouse_step_begin(self._h, Hv.handle, Beta.handle, V.handle, W.handle, wcol, k, slot)
+        if rc == HOUSE_NOT_SERVED:
+            return None
+        _check(self._lib, rc, "kh_zhouse_step_begin")
+        raw = numpy.empty(2 * (k + 1) + 7, dtype=numpy.float64)
+        rc = self._lib.kh_zhouse_step_end(self._h, slot, raw.size, _dptr(raw))
+        if rc == HOUSE_TIMED_OUT:
+            return False
+        _check(self._lib, rc, "kh_zhouse_step_end")
+        out = numpy.empty(k + 6, dtype=numpy.complex128)
+        out[: k + 1] = raw[: 2 * (k + 1)].view(numpy.complex128)
+        s = raw[2 * (k + 1):]          # Re gamma, Im gamma, sigma^2, xnorm, Re alpha, Im alpha, beta
+        out[k + 1:] = [complex(s[0], s[1]), s[2], s[3], complex(s[4], s[5]), s[6]]
         return out
 
     def residual(self, A, B, bcol, X, xcol, R, rcol):

@@ -1,17 +1,21 @@
-// Householder Arnoldi in one launch per step (house.h): the launcher of k_house_chain and the entry pair
-// kh_house_step_begin / _end.  A translation unit of its own - the twelve instantiations are compiled here.
+// Householder Arnoldi in one launch per step (house.h): the launcher of k_house_chain (real) and k_zhouse_chain (complex
+// data: the (re, im) views of c128 blocks) and the entry pairs kh_house_step_begin / _end and kh_zhouse_step_begin / _end.
+// A translation unit of its own - the twelve real and ten complex instantiations are compiled here.
 //
-// Shapes: the rows-per-lane classes of the plain chain family on one GPU, 4 ... 40 double2 rows per lane, each as the
+// Shapes: the rows-per-lane classes of the plain chain family on one GPU, 4 ... 40 double2 rows per lane (complex: 4 ... 32,
+// the 40-row complex kernel spills in its streaming loops and is not compiled), each as the
 // predicate-free kernel (every block padded to whole workgroup chunks: kh_vec_alloc) and as the MASKED one (short or
 // unpadded vectors, a partial last workgroup).  Everything else is declined with KH_HOUSE_NOT_SERVED and the host layer
 // applies the reflectors one by one as before: longer vectors (w would need LDS beside the registers), a communicator,
-// k + 1 >= N (no reflector is left to make), k + 2 > 1024 (the raw H entries are taken from workgroup 0's first row), more
+// k + 1 >= N (no reflector is left to make), k + 2 > 1024 (the raw H entries are taken from workgroup 0's first row - complex: its first two rows), more
 // workgroups than the XCD-leader form of the sums takes (256), a refused launch (occupancy: remembered for that length).
 //
 // A timed-out sum (the error word, or the "chain_fault" fake) is reported by kh_house_step_end as KH_HOUSE_TIMED_OUT: the
 // kernel has not touched A v_k, so the host re-runs the step on the per-reflector path, which overwrites column k + 1 of both
 // blocks and beta[k + 1].  The error word is cleared there and the family is armed again for the next step; the third
 // timeout in one context leaves it off (kh_ctx_set "house_chain" 1 starts the count again) - the chain kernels' limit.
+// Switch and count are shared by the real and the complex step; the launches are counted apart (n_house_chain,
+// n_zhouse_chain), and so is the length whose launch was refused.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -20,12 +24,16 @@
 
 namespace kh {
 
-template <int R2, bool MASKED>
+template <int R2, bool MASKED, bool CPLX = false>
 static hipError_t launch_house(kh_ctx ctx, int G, HouseArgs& a) {
     // (cached per process like launch_chain's: one context = one device = one process, single-threaded by the contract
     // of krylov_hip.h; a second device of another kind in the same process would need the figure per context)
     static int blocks_per_cu = -1;
-    auto kern = k_house_chain<R2, MASKED>;
+    // (if constexpr: a real launcher must not instantiate the complex kernel of its shape - the 40-row one is not shipped)
+    auto kern = [] {
+        if constexpr (CPLX) return k_zhouse_chain<R2, MASKED>;
+        else return k_house_chain<R2, MASKED>;
+    }();
     if (blocks_per_cu < 0) {
         int nb = 0;
         hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, CH_BS, 0);
@@ -42,27 +50,35 @@ static hipError_t launch_house(kh_ctx ctx, int G, HouseArgs& a) {
 
 using namespace kh;
 
-extern "C" {
-
-int kh_house_step_begin(kh_ctx ctx, kh_vec Hv, kh_vec Beta, kh_vec V, kh_vec W, int64_t wcol, int64_t k, int slot) {
-    KH_ARG(ctx && Hv && Beta && V && W, "kh_house_step_begin: NULL argument");
-    KH_ARG(slot >= 0 && slot < KH_NSLOT, "kh_house_step_begin: slot %d not in [0,%d)", slot, KH_NSLOT);
+// Both entries: `cplx` - Hv, V, W are the (re, im) views of complex blocks (one double2 row = one complex row, N = n / 2),
+// the kernel is k_zhouse_chain and the H column holds 2 (k + 1) + ZHOUSE_NSCAL doubles.
+static int house_begin(kh_ctx ctx, kh_vec Hv, kh_vec Beta, kh_vec V, kh_vec W, int64_t wcol, int64_t k, int slot, bool cplx) {
+    const char* who = cplx ? "kh_zhouse_step_begin" : "kh_house_step_begin";
+    KH_ARG(ctx && Hv && Beta && V && W, "%s: NULL argument", who);
+    KH_ARG(slot >= 0 && slot < KH_NSLOT, "%s: slot %d not in [0,%d)", who, slot, KH_NSLOT);
     KH_ARG(k >= 0 && k + 1 < V->ncols && k + 1 < Hv->ncols,
-           "kh_house_step_begin: k=%lld needs %lld columns, the basis has %lld, the reflector block %lld", (long long)k,
+           "%s: k=%lld needs %lld columns, the basis has %lld, the reflector block %lld", who, (long long)k,
            (long long)(k + 2), (long long)V->ncols, (long long)Hv->ncols);
-    KH_ARG(Beta->ncols >= 1 && Beta->n >= k + 2, "kh_house_step_begin: the beta array holds %lld entries, step %lld writes entry %lld",
+    KH_ARG(Beta->ncols >= 1 && Beta->n >= k + 2, "%s: the beta array holds %lld entries, step %lld writes entry %lld", who,
            (long long)Beta->n, (long long)k, (long long)(k + 1));
-    KH_TRY(check_vec(W, wcol, 1, "kh_house_step_begin(W)"));
-    KH_ARG(Hv->n == V->n && W->n == V->n, "kh_house_step_begin: lengths differ");
-    RoctxScope range_(ctx, "kh_house_step_begin k=%lld", (long long)k);
-    const int64_t n = V->n;
+    KH_TRY(check_vec(W, wcol, 1, cplx ? "kh_zhouse_step_begin(W)" : "kh_house_step_begin(W)"));
+    KH_ARG(Hv->n == V->n && W->n == V->n, "%s: lengths differ", who);
+    KH_ARG(!cplx || (V->n & 1) == 0, "%s: a complex view has an even length, this one %lld", who, (long long)V->n);
+    RoctxScope range_(ctx, cplx ? "kh_zhouse_step_begin k=%lld" : "kh_house_step_begin k=%lld", (long long)k);
+    const int64_t n = V->n;                  // doubles
+    const int64_t rows = cplx ? n / 2 : n;   // rows of the vector: N
     if (!ctx->house_chain || ctx->house_recoveries >= KH_CHAIN_MAX_RECOVERIES || kh_multi(ctx)) return KH_HOUSE_NOT_SERVED;
-    if (k + 1 >= n || k + 2 > 2 * CH_BS || n == ctx->house_refused_n) return KH_HOUSE_NOT_SERVED;
+    int64_t& refused_n = cplx ? ctx->zhouse_refused_n : ctx->house_refused_n;
+    if (k + 1 >= rows || k + 2 > 2 * CH_BS || n == refused_n) return KH_HOUSE_NOT_SERVED;
     int r2 = 0, G = 0;
     if (!chain_geometry(ctx, n, &r2, &G) || r2 > 40 || 2 * G > CH_BS) return KH_HOUSE_NOT_SERVED;
+    // k_zhouse_chain<40, *> keeps rows of w in scratch: 82 / 116 spilled registers (120 / 224 B per lane) with loads and
+    // stores inside the dot and update phases of every link (profiles/zhouse_chain_resource_usage.txt) - not shipped, the
+    // 40-row class of complex vectors (N > 32 * 512 * CUs) stays on the per-reflector path
+    if (cplx && r2 > ZHOUSE_MAX_R2) return KH_HOUSE_NOT_SERVED;
     // (an odd n is handled as n + 1: row n must exist behind every column)
     if ((n & 1) && (V->ld <= n || Hv->ld <= n || W->ld <= n)) return KH_HOUSE_NOT_SERVED;
-    KH_TRY(ensure_hcap(ctx, k + 1 + HOUSE_NSCAL));
+    KH_TRY(ensure_hcap(ctx, cplx ? 2 * (k + 1) + ZHOUSE_NSCAL : k + 1 + HOUSE_NSCAL));
     KH_TRY(chain_epoch_check(ctx));
     const int64_t chunk2 = (int64_t)r2 * CH_BS;
     // predicate-free kernel iff every block involved is padded to G whole chunks
@@ -94,26 +110,38 @@ int kh_house_step_begin(kh_ctx ctx, kh_vec Hv, kh_vec Beta, kh_vec V, kh_vec W, 
         ctx->done_seq[slot] = a.done_tag;
     }
     hipError_t e;
-#define KH_HOUSE(R) (padded ? launch_house<R, false>(ctx, G, a) : launch_house<R, true>(ctx, G, a))
-    switch (r2) {
-        case 4: e = KH_HOUSE(4); break;
-        case 8: e = KH_HOUSE(8); break;
-        case 16: e = KH_HOUSE(16); break;
-        case 24: e = KH_HOUSE(24); break;
-        case 32: e = KH_HOUSE(32); break;
-        default: e = KH_HOUSE(40); break;
+#define KH_HOUSE(R, C) (padded ? launch_house<R, false, C>(ctx, G, a) : launch_house<R, true, C>(ctx, G, a))
+    if (cplx) {
+        switch (r2) {        // (40 rows: declined above)
+            case 4: e = KH_HOUSE(4, true); break;
+            case 8: e = KH_HOUSE(8, true); break;
+            case 16: e = KH_HOUSE(16, true); break;
+            case 24: e = KH_HOUSE(24, true); break;
+            default: e = KH_HOUSE(32, true); break;
+        }
+    } else {
+        switch (r2) {
+            case 4: e = KH_HOUSE(4, false); break;
+            case 8: e = KH_HOUSE(8, false); break;
+            case 16: e = KH_HOUSE(16, false); break;
+            case 24: e = KH_HOUSE(24, false); break;
+            case 32: e = KH_HOUSE(32, false); break;
+            default: e = KH_HOUSE(40, false); break;
+        }
     }
 #undef KH_HOUSE
     if (e != hipSuccess) {
         // e.g. hipErrorCooperativeLaunchTooLarge: not all workgroups can be co-resident.  A property of this shape on this
         // device: vectors of this length take the per-reflector path from now on
         (void)hipGetLastError();
-        ctx->house_refused_n = n;
+        refused_n = n;
         return KH_HOUSE_NOT_SERVED;
     }
     if (a.debug == 4) ctx->chain_fault = 0;
-    ctx->n_house_chain += 1;
-    ctx->chain_epoch += (unsigned)(2 * k + 3);     // at most: k + 1 forward links, the reflector's pair, k + 1 backward links
+    if (cplx) ctx->n_zhouse_chain += 1;
+    else ctx->n_house_chain += 1;
+    // at most: k + 1 forward links, the reflector's round (complex: a pair and a single), k + 1 backward links
+    ctx->chain_epoch += (unsigned)(2 * k + (cplx ? 4 : 3));
     ctx->step[slot].kind = 0;                      // (no Gram-Schmidt step is parked in this slot any more)
     chain_blk_touch(ctx, V);
     ctx->wait_tag[slot] = a.donepin != nullptr;
@@ -121,12 +149,25 @@ int kh_house_step_begin(kh_ctx ctx, kh_vec Hv, kh_vec Beta, kh_vec V, kh_vec W, 
     return 0;
 }
 
-int kh_house_step_end(kh_ctx ctx, int slot, int64_t count, double* out) {
-    KH_ARG(ctx && out, "kh_house_step_end: NULL");
-    KH_ARG(slot >= 0 && slot < KH_NSLOT && count >= 0 && count <= ctx->hcap, "kh_house_step_end: slot %d / count %lld", slot,
+extern "C" {
+
+int kh_house_step_begin(kh_ctx ctx, kh_vec Hv, kh_vec Beta, kh_vec V, kh_vec W, int64_t wcol, int64_t k, int slot) {
+    return house_begin(ctx, Hv, Beta, V, W, wcol, k, slot, false);
+}
+
+int kh_zhouse_step_begin(kh_ctx ctx, kh_vec Hv, kh_vec Beta, kh_vec V, kh_vec W, int64_t wcol, int64_t k, int slot) {
+    return house_begin(ctx, Hv, Beta, V, W, wcol, k, slot, true);
+}
+
+// (the slot does not know what kind of step was begun in it: waiting, the error word and the recovery count are the same)
+static int house_end(kh_ctx ctx, int slot, int64_t count, double* out, bool cplx) {
+    const char* who = cplx ? "kh_zhouse_step_end" : "kh_house_step_end";
+    KH_ARG(ctx && out, "%s: NULL", who);
+    KH_ARG(slot >= 0 && slot < KH_NSLOT && count >= 0 && count <= ctx->hcap, "%s: slot %d / count %lld", who, slot,
            (long long)count);
-    KH_ARG(ctx->hev[slot] != nullptr, "kh_house_step_end: no step was begun");
-    RoctxScope range_(ctx, "kh_house_step_end slot=%lld count=%lld", (long long)slot, (long long)count);
+    KH_ARG(ctx->hev[slot] != nullptr, "%s: no step was begun", who);
+    RoctxScope range_(ctx, cplx ? "kh_zhouse_step_end slot=%lld count=%lld" : "kh_house_step_end slot=%lld count=%lld",
+                      (long long)slot, (long long)count);
     KH_TRY(wait_slot(ctx, slot));
     if (*ctx->chain_err_pin[slot] != 0) {
         // a grid-wide sum of the launch timed out (its workgroups were not co-resident: a shared GPU): column k + 1 of both
@@ -145,5 +186,9 @@ int kh_house_step_end(kh_ctx ctx, int slot, int64_t count, double* out) {
     memcpy(out, ctx->hslot_pin[slot], sizeof(double) * count);
     return 0;
 }
+
+int kh_house_step_end(kh_ctx ctx, int slot, int64_t count, double* out) { return house_end(ctx, slot, count, out, false); }
+
+int kh_zhouse_step_end(kh_ctx ctx, int slot, int64_t count, double* out) { return house_end(ctx, slot, count, out, true); }
 
 }  // extern "C"

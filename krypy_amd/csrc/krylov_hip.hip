@@ -1673,6 +1673,7 @@ int kh_ctx_set(kh_ctx ctx, const char* key, int64_t value) {
         ctx->house_chain = value != 0;
         ctx->house_recoveries = 0;          // (an explicit setting starts the count again)
         ctx->house_refused_n = -1;
+        ctx->zhouse_refused_n = -1;
     }
     else if (!strcmp(key, "chain_epoch")) ctx->chain_epoch = (unsigned)value;      // tests: bring the epoch counter of the grid-wide sums near its wrap
     else if (!strcmp(key, "chain_debug")) ctx->chain_debug = (int)value;    // measurement: phases switched off (garbage results)
@@ -1745,6 +1746,7 @@ int kh_ctx_get(kh_ctx ctx, const char* key, int64_t* value) {
     else if (!strcmp(key, "n_chain_recovered")) *value = ctx->n_chain_recovered;
     else if (!strcmp(key, "house_chain")) *value = ctx->house_chain;
     else if (!strcmp(key, "n_house_chain")) *value = ctx->n_house_chain;
+    else if (!strcmp(key, "n_zhouse_chain")) *value = ctx->n_zhouse_chain;
     else if (!strcmp(key, "n_house_recovered")) *value = ctx->n_house_recovered;
     else if (!strcmp(key, "chain_epoch")) *value = ctx->chain_epoch;
     else if (!strcmp(key, "n_epoch_wraps")) *value = ctx->n_epoch_wraps;

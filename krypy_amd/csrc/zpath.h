@@ -7,7 +7,8 @@
 // coefficients, complex CSR / dense / diagonal operators, and the Arnoldi step built from them.
 // Arithmetic follows NumPy's complex formulas ((ar*br - ai*bi), (ar*bi + ai*br), separate
 // roundings; -ffp-contract=off), CSR rows are summed left to right like scipy's csr_matvec.
-// Correctness first: per-column launches (no register-resident chain yet).
+// The kernels of this file are per-column launches; the register-resident complex chains are instantiations of the
+// chain kernels themselves (chain.h: k_mgs_chain<..., CPLX>) and the one-launch Householder step (house.h: k_zhouse_chain).
 #pragma once
 // included at the end of krylov_hip.hip (one translation unit: the kernels of kernels.h are shared)
 

@@ -460,7 +460,9 @@ class _FusedHouse(_DevHouse):
 
     def __init__(self, ctx, Hv, j, alpha, beta, xnorm):
         self.ctx, self.Hv, self.j = ctx, Hv, j
-        self.alpha, self.beta, self.xnorm = float(alpha), float(beta), float(xnorm)
+        # (a complex basis keeps a complex alpha: ``Context.zhouse_step``)
+        self.alpha = complex(alpha) if numpy.iscomplexobj(alpha) else float(alpha)
+        self.beta, self.xnorm = float(numpy.real(beta)), float(numpy.real(xnorm))
 
 
 # ----------------------------------------------------------------------------------------
@@ -1053,7 +1055,7 @@ class Arnoldi(object):
         :param v: initial vector, ``(N,1)`` ndarray (or a :class:`DVec`).
         :param maxiter: maximal number of iterations (default ``N``).
         :param ortho: ``'mgs'`` (default), ``'dmgs'``, ``'lanczos'``, ``'house'`` as in the reference
-            (``'house'``: real data on one GPU takes one launch per step, ``k_house_chain``; everything
+            (``'house'``: data on one GPU takes one launch per step, ``k_house_chain`` / ``k_zhouse_chain``; everything
             else applies the reflectors one by one), plus the extensions ``'cgs'`` / ``'cgs2'`` (panel
             Gram-Schmidt, one / two passes).
         :param M: self-adjoint positive definite preconditioner; then ``P`` with ``V = M P``
@@ -1173,13 +1175,14 @@ class Arnoldi(object):
             # own (N, maxiter+2) block.  Sequential like modified Gram-Schmidt, and run the same way: a
             # context that offers `house_step` applies all reflectors of a step, makes the new one and
             # builds v_{k+1} in ONE launch (csrc/house.h) with the factors beta_j in a device array of
-            # this object's; steps it declines (complex data, N ranks, long vectors) and contexts
-            # without it apply every reflector as a device dot + axpy (_advance_house).
+            # this object's (complex data: `zhouse_step`, the factors stay real); steps it declines (N ranks,
+            # long vectors) and contexts without it apply every reflector as a device dot + axpy
+            # (_advance_house).
             self._fused, self._lookahead = False, 0
             self._Hv = ctx.alloc(N, min(self.maxiter + 1, N) + 1, dtype=bdt)
             self._Hbeta = None
-            if getattr(ctx, "house_step", None) is not None and not cplx:
-                self._Hbeta = ctx.alloc(self._Hv.ncols, 1, dtype=bdt)
+            if getattr(ctx, "zhouse_step" if cplx else "house_step", None) is not None:
+                self._Hbeta = ctx.alloc(self._Hv.ncols, 1, dtype=numpy.float64)
 
         # A preconditioner that is NOT a device matrix (a callable such as an incomplete-factorisation solve, a
         # composite operator): the Gram-Schmidt part of the step does not depend on M at all - coefficients against
@@ -1452,13 +1455,13 @@ class Arnoldi(object):
     def _put_beta(self, j):
         """Reflector ``j`` was made on the per-reflector path: the one-launch step reads its factor from the device."""
         if self._Hbeta is not None:
-            self._Hbeta.set(0, j, [float(self.houses[j].beta)])
+            self._Hbeta.set(0, j, [float(numpy.real(self.houses[j].beta))])
 
     def _advance_house(self, k):
         """One Householder Arnoldi step (utils.py:970-994) on the device."""
         ctx, V, W, H, N = self._ctx, self._V, self._W, self.H, self._V.n
         self.A._apply_dev(V, k, W, 0, 1)
-        step = getattr(ctx, "house_step", None) if self._Hbeta is not None else None
+        step = getattr(ctx, "zhouse_step" if self._cplx else "house_step", None) if self._Hbeta is not None else None
         if step is not None:
             # one launch, one host wait.  Rows 0 .. k come back without the factors conj(alpha_j) (no later reflector
             # reads row j: applied here), H[k+1, k] is the new reflector's xnorm, its scalars come along.  None: the
@@ -1470,7 +1473,7 @@ class Arnoldi(object):
             if out is not None and out is not False:
                 alphas = numpy.array([h.alpha for h in self.houses[: k + 1]])
                 H[: k + 1, k] = out[: k + 1] * numpy.conj(alphas)
-                xnorm, alpha, beta = out[k + 3], out[k + 4], out[k + 5]
+                xnorm, alpha, beta = numpy.real(out[k + 3]), out[k + 4], numpy.real(out[k + 5])
                 H[k + 1, k] = xnorm
                 self.houses.append(_FusedHouse(ctx, self._Hv, k + 1, alpha, beta, xnorm))
                 return float(xnorm)

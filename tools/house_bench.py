@@ -8,7 +8,10 @@ outside the timed region), device calls per step (every call of the host layer t
 copy: operator, dot / axpy panels, entry reads and writes, the step kernels) and host waits per step (calls that return
 device data to the host).  A device call is NOT a launch - one call may enqueue several kernels or copies; only the
 k_house_chain count is exact.  Kernel launches per step come from a kernel trace of a fused run (rocprofv3 --kernel-trace).
-    python tools/house_bench.py [nx ...]"""
+
+--c128: the same on complex data - the Laplacian minus the shift (0.5 + 0.75i) I, a complex start vector; the one-launch
+step is k_zhouse_chain (counter n_zhouse_chain), the columns are the same.  --reps R: timed repetitions (default 3).
+    python tools/house_bench.py [--c128] [--reps R] [nx ...]"""
 import os
 import sys
 import time
@@ -19,10 +22,10 @@ STEPS = 100
 REPS = 3
 
 # methods of the context / of a device block that enqueue work; the ones in WAITS hand device data back to the host
-CTX_CALLS = ("apply", "dot_panel", "axpy_panel", "nrm2", "vdiv", "waxpby", "house_step", "arnoldi_step", "arnoldi_step_begin",
-             "arnoldi_step_end")
+CTX_CALLS = ("apply", "dot_panel", "axpy_panel", "nrm2", "vdiv", "waxpby", "house_step", "zhouse_step", "arnoldi_step",
+             "arnoldi_step_begin", "arnoldi_step_end")
 VEC_CALLS = ("get", "set", "zero", "zero_range", "copy_from")
-WAITS = ("dot_panel", "nrm2", "house_step", "arnoldi_step", "arnoldi_step_end", "get")
+WAITS = ("dot_panel", "nrm2", "house_step", "zhouse_step", "arnoldi_step", "arnoldi_step_end", "get")
 
 
 class Tally(object):
@@ -31,7 +34,9 @@ class Tally(object):
         self._undo = []
         for owner, names in ((type(ctx), CTX_CALLS), (vec_cls, VEC_CALLS)):
             for name in names:
-                fn = getattr(owner, name)
+                fn = getattr(owner, name, None)
+                if fn is None:          # (a context without the complex step)
+                    continue
                 setattr(owner, name, self._wrap(name, fn))
                 self._undo.append((owner, name, fn))
 
@@ -57,29 +62,43 @@ def run(ctx, utils, A, v, ortho, steps):
     return time.perf_counter() - t0
 
 
-def main(sizes):
+def counter_of(ctx, key):
+    """A counter of the context, 0 where the library does not know it (a build without the complex step)."""
+    try:
+        return ctx.get(key)
+    except Exception:
+        return 0
+
+
+def main(sizes, c128=False, reps=REPS):
     import numpy as np
+    import scipy.sparse as sp
     import bench
     from krypy_amd import _hip, utils
 
     ctx = _hip.get_context()
     variants = (("house fused", "house", 1), ("house per-reflector", "house", 0), ("mgs", "mgs", 1))
+    counter, kernel = ("n_zhouse_chain", "k_zhouse_chain") if c128 else ("n_house_chain", "k_house_chain")
     for nx in sizes:
         A = bench.laplace2d(nx, nx)
         N = A.shape[0]
-        v = np.random.default_rng(0).standard_normal((N, 1))
+        rng = np.random.default_rng(0)
+        v = rng.standard_normal((N, 1))
+        if c128:
+            A = (A.astype(np.complex128) - (0.5 + 0.75j) * sp.identity(N, dtype=np.complex128, format="csr")).tocsr()
+            v = v + 1j * rng.standard_normal((N, 1))
         best, counts = {}, {}
         for name, ortho, sw in variants:                 # warm-up (code objects, the operator's upload) + the call counts
             ctx.set("house_chain", sw)
-            k0, w0 = ctx.get("n_house_chain"), ctx.get("n_tag_waits")
+            k0, w0 = counter_of(ctx, counter), ctx.get("n_tag_waits")
             tally = Tally(ctx, _hip.DeviceVectors)
             try:
                 run(ctx, utils, A, v, ortho, STEPS)
             finally:
                 tally.close()
-            counts[name] = (tally.calls / STEPS, tally.waits / STEPS, (ctx.get("n_house_chain") - k0) / STEPS,
+            counts[name] = (tally.calls / STEPS, tally.waits / STEPS, (counter_of(ctx, counter) - k0) / STEPS,
                             (ctx.get("n_tag_waits") - w0) / STEPS)
-        for _ in range(REPS):                            # alternating: a drift of the machine hits all three alike
+        for _ in range(reps):                            # alternating: a drift of the machine hits all three alike
             for name, ortho, sw in variants:
                 ctx.set("house_chain", sw)
                 dt = run(ctx, utils, A, v, ortho, STEPS)
@@ -88,12 +107,17 @@ def main(sizes):
         for name, _, _ in variants:
             r = sorted(best[name])
             c = counts[name]
-            print("N = %8d  %-20s %9.1f steps/s (median of %d; %.1f ... %.1f)  device calls/step %6.1f  host waits/step %6.1f"
-                  "  k_house_chain launches/step %.2f  completion-tag waits/step %.2f"
-                  % (N, name, r[len(r) // 2], REPS, r[0], r[-1], c[0], c[1], c[2], c[3]), flush=True)
-        f, p = sorted(best["house fused"])[REPS // 2], sorted(best["house per-reflector"])[REPS // 2]
+            print("N = %8d  %s %-20s %9.1f steps/s (median of %d; %.1f ... %.1f)  device calls/step %6.1f  host waits/step %6.1f"
+                  "  %s launches/step %.2f  completion-tag waits/step %.2f"
+                  % (N, "c128" if c128 else "f64 ", name, r[len(r) // 2], reps, r[0], r[-1], c[0], c[1], kernel, c[2], c[3]),
+                  flush=True)
+        f, p = sorted(best["house fused"])[reps // 2], sorted(best["house per-reflector"])[reps // 2]
         print("N = %8d  fused / per-reflector = %.2f x" % (N, f / p), flush=True)
 
 
 if __name__ == "__main__":
-    main([int(a) for a in sys.argv[1:]] or [100, 316, 1000, 3162])
+    args = sys.argv[1:]
+    c128 = "--c128" in args
+    reps = int(args[args.index("--reps") + 1]) if "--reps" in args else REPS
+    sizes = [int(a) for i, a in enumerate(args) if not a.startswith("--") and (i == 0 or args[i - 1] != "--reps")]
+    main(sizes or [100, 316, 1000, 3162], c128=c128, reps=reps)
