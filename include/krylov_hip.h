@@ -74,7 +74,8 @@ int kh_ctx_counters(kh_ctx ctx, int64_t out[4]);
 int kh_ctx_tune(kh_ctx ctx, int reduce_blocks, int spmv_tile);
 /* named switches of a context (1 = on, the default; the environment variables of INTEGRATION.md set the
  * initial values): "spmv_dia" banded SpMV for stencil CSR operators, "chain" register-resident MGS chain,
- * "chain_lds" column head parked in LDS, "chain_spmv" operator fused into the chain prologue, "chain_onex" short vectors
+ * "chain_lds" column head parked in LDS, "chain_spmv" operator fused into the chain prologue ("chain_xwin": its
+ * mask form reads x through an LDS window; kh_ctx_get("n_chain_xwin") counts those launches), "chain_onex" short vectors
  * on one XCD, "chain_small" the column-ring kernel for them, "lanczos_fused" the three-pass Lanczos kernel, "tag_wait"
  * completion tags in pinned memory instead of an event per Arnoldi step, "house_chain" the one-launch Householder step
  * (kh_house_step_begin; 0: the caller's per-reflector path).  bench.py

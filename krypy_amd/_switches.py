@@ -26,6 +26,10 @@ SWITCHES = [
      "kernel.  Same bits either way"),
     ("KRYPY_AMD_CHAIN_SPMV", "1", "kernel-path", "0",
      "0: banded operators are applied by a separate SpMV launch instead of in the chain kernel's prologue.  Same bits either way"),
+    ("KRYPY_AMD_CHAIN_XWIN", "1", "kernel-path", "0",
+     "0: the mask-form operator prologue of `k_mgs_chain_lds` (16 ... 40 rows per lane) reads x through clamped global gathers instead "
+     "of through its LDS window (`csrc/chain.h`: `chain_apply_banded_xwin`; taken when the band fits the ring of 15 / 12 blocks of "
+     "1024 doubles).  Same bits either way; counter `n_chain_xwin`"),
     ("KRYPY_AMD_CHAIN_LDS", "1", "kernel-path", "0", "0: plain chain kernel (no LDS / register-ring reuse of the column)"),
     ("KRYPY_AMD_CHAIN_PF", "1", "kernel-path", "0",
      "0: never use `k_mgs_chain_pf` (LDS-DMA re-reads, next column prefetched through the update phase; used up to 24 rows per lane); "

@@ -80,6 +80,9 @@ struct ChainArgs {
     const double* xk;
     int64_t n_last;    // n - 1
     DiaOffs offs;
+    // k_mgs_chain_lds, mask form: 1 = the prologue reads x through its LDS window (chain_apply_banded_xwin; the launcher has
+    // checked that the band fits), 0 = through clamped gathers.  Every other kernel ignores it
+    int xwin;
     // short vectors, all working workgroups on ONE XCD (ONEX instantiations): 8 G + 8 workgroups are launched, those
     // that do not run on XCD `onex_target` leave at once, the others draw a ticket and the first onex_G of them work
     int onex_G;
@@ -753,6 +756,153 @@ __device__ __forceinline__ void chain_apply_banded_form(const ChainArgs& a, int6
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// The x window: a workgroup's rows of w = A x are one contiguous chunk of x indices, and every neighbour a row needs lies
+// within [off_min, off_max] of it.  So the workgroup copies x ONCE, block by block (one block = the CH_BS double2 of one
+// row of the chunk, loaded coalesced and non-temporally, ONE clamp per 16-byte row), into a ring of NWB blocks in LDS, and the
+// lanes take all 2 FND neighbour values of a row pair from there: no 64-bit clamps, no global gathers, every element of
+// x through the vector memory path once (plus the halo blocks) instead of FND times.
+//
+// Layout: the ring is DE-INTERLEAVED - the even elements of x in the first half (H = NWB * CH_BS doubles), the odd ones
+// in the second - so that consecutive lanes (rows 2 i2 + off, stride two doubles) read consecutive doubles: no bank
+// conflicts.  Block q (relative to the workgroup's first row, q = LO ... R2 - 1 + HI with LO = floor(off_min / 1024),
+// HI = ceil(off_max / 1024)) sits in slot (q - LO) mod NWB.  Element x[2 (i2 + r CH_BS) + o] of lane tid, row r:
+//     half-index  (r mod NWB) * CH_BS + tid + k(o),   k(o) = (o >> 1) - LO * CH_BS  in [0, H),   wrapped ONCE at H,
+//     in the half of parity o & 1
+// - the lane's own window position plus a per-diagonal (wave-uniform) constant.
+// Row r needs blocks r + LO ... r + HI; block r + HI + 1 is written while row r is computed, so the launcher takes the
+// window only when HI - LO + 2 <= NWB (xwin_fits).  What the ring holds for indices before row 0 and behind row n - 1 are
+// clamped copies: values of slots without an entry, which the arithmetic never uses (the selects of the row loop).
+// ------------------------------------------------------------------------------------------
+struct XwinGeom {
+    int lo, hi;                  // blocks before / behind a row's own that it reads from
+};
+__host__ __device__ __forceinline__ XwinGeom xwin_geom(const DiaOffs& o, int nd) {
+    int mn = 0, mx = 0;
+    for (int d = 0; d < nd; ++d) {
+        mn = o.off[d] < mn ? o.off[d] : mn;
+        mx = o.off[d] > mx ? o.off[d] : mx;
+    }
+    XwinGeom g;
+    g.lo = mn >> 10;             // floor(mn / (2 CH_BS)); an arithmetic shift
+    g.hi = (mx + 1023) >> 10;    // the last lane's odd row reads element 1022 + mx + 1 of the row's block
+    return g;
+}
+static_assert(2 * CH_BS == 1024, "xwin_geom counts blocks of 2 CH_BS doubles");
+// does the band fit a ring of nwb blocks?  (all or nothing per launch: the host decides)
+__host__ __device__ __forceinline__ bool xwin_fits(const DiaOffs& o, int nd, int nwb) {
+    const XwinGeom g = xwin_geom(o, nd);
+    return g.hi - g.lo + 2 <= nwb;
+}
+
+template <int NWB>
+struct XWindow {
+    static constexpr unsigned H = (unsigned)NWB * CH_BS;      // doubles per half
+    double* win;                 // LDS: [2][NWB][CH_BS] doubles
+    const double2* x2;           // x as 16-byte rows
+    int64_t i2_last;             // last 16-byte row that holds an element of x
+    // stage: the global half (issued early) ...
+    __device__ __forceinline__ double2 load(int64_t i2) const {
+        i2 = i2 < 0 ? 0 : (i2 > i2_last ? i2_last : i2);
+        return ld_nt2(x2 + i2);
+    }
+    // ... and the LDS half (slot = the block's place in the ring)
+    __device__ __forceinline__ void store(unsigned slot, int tid, double2 v) const {
+        win[slot * CH_BS + tid] = v.x;
+        win[H + slot * CH_BS + tid] = v.y;
+    }
+    // get: the lane's position pos = (r mod NWB) * CH_BS + tid, the diagonal's constants k (< H) and half (0 or H)
+    __device__ __forceinline__ double get(unsigned pos, unsigned k, unsigned half) const {
+        const unsigned v = pos + k;
+        const unsigned u = v - H;
+        return win[(u < v ? u : v) + half];       // (v < H: u wraps to a huge number and v wins)
+    }
+};
+
+// The third form of the row loop: mask form, x through the window.  The arithmetic is chain_apply_banded_form<MASK = true>'s
+// - dia_slot, ascending offsets, separate multiply and add, empty slots skipped - on the same values of x: the same bits.
+// Straight-line code for all 512 threads, R2 + 1 workgroup barriers (ch_lds_barrier: the staged loads stay in flight across
+// them), none of them under a condition.  D blocks of x and D rows of masks are in flight ahead of the row in work.
+template <int R2, int FND, int NWB, int D, class Put>
+__device__ __forceinline__ void chain_apply_banded_xwin(const ChainArgs& a, int64_t first, double* win, Put&& put) {
+    static_assert(D >= 1 && D < R2, "blocks staged ahead");
+    const int tid = threadIdx.x;
+    XWindow<NWB> xw;
+    xw.win = win;
+    xw.x2 = reinterpret_cast<const double2*>(a.xk);
+    xw.i2_last = a.n_last >> 1;
+    constexpr unsigned H = XWindow<NWB>::H;
+    const XwinGeom g = xwin_geom(a.offs, FND);
+    const int spanb = g.hi - g.lo + 1;             // blocks a row reads from (<= NWB - 1)
+    unsigned kq[FND][2], kh[FND][2];               // wave-uniform
+#pragma unroll
+    for (int d = 0; d < FND; ++d) {
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+            const int o = a.offs.off[d] + p;
+            kq[d][p] = (unsigned)((o >> 1) - g.lo * CH_BS);
+            kh[d][p] = (o & 1) ? H : 0u;
+        }
+    }
+    // the blocks of row 0: slots 0 ... spanb - 1 (the slots behind them get a copy of the last one: written again in time)
+    {
+        const int64_t b0 = first + (int64_t)g.lo * CH_BS;
+        constexpr int PG = 8;                      // loads in flight
+#pragma unroll
+        for (int j0 = 0; j0 < NWB - 1; j0 += PG) {
+            double2 t[PG];
+#pragma unroll
+            for (int j = j0; j < j0 + PG && j < NWB - 1; ++j) t[j - j0] = xw.load(b0 + (int64_t)(j < spanb ? j : spanb - 1) * CH_BS);
+            CH_ISSUE_FENCE();
+#pragma unroll
+            for (int j = j0; j < j0 + PG && j < NWB - 1; ++j) xw.store((unsigned)j, tid, t[j - j0]);
+        }
+    }
+    double2 st[D];
+    unsigned mk[D];
+    int64_t fb = first;          // passed through an opaque asm every row, like chain_apply_banded_form's: the addresses of the
+                                 // rows to come are not formed (and kept) ahead of their loads
+    const int64_t hs = (int64_t)(g.hi + 1) * CH_BS;              // block hi + 1 + r is written while row r is in work
+#pragma unroll
+    for (int r = 0; r < D; ++r) {
+        mk[r] = dia_mask_load(a.dmask, fb + (int64_t)r * CH_BS);
+        st[r] = xw.load(fb + hs + (int64_t)r * CH_BS);
+    }
+    unsigned sl = (unsigned)spanb;                 // slot of block hi + 1
+    unsigned tb = (unsigned)tid;                   // (opaque per row as well: the ring's addresses repeat every NWB rows and would
+                                                   // otherwise be kept in registers from one use to the next)
+    ch_lds_barrier();
+#pragma unroll
+    for (int r = 0; r < R2; ++r) {
+        const unsigned m = mk[r % D];
+        const unsigned pos = (unsigned)((r % NWB) * CH_BS) + tb;
+        double2 av[FND];
+        double x0[FND], x1[FND];
+#pragma unroll
+        for (int d = 0; d < FND; ++d) {
+            av[d] = dia_slot<true>(a.dia, a.dia_ld, d, 0, m, a.offs.cst[d]);
+            x0[d] = xw.get(pos, kq[d][0], kh[d][0]);
+            x1[d] = xw.get(pos, kq[d][1], kh[d][1]);
+        }
+        double s0 = 0.0, s1 = 0.0;
+#pragma unroll
+        for (int d = 0; d < FND; ++d) {
+            const double p0 = av[d].x * x0[d], p1 = av[d].y * x1[d];
+            s0 = (av[d].x != 0.0) ? s0 + p0 : s0;
+            s1 = (av[d].y != 0.0) ? s1 + p1 : s1;
+        }
+        put(r, s0, s1);
+        if (r + 1 < R2) {
+            xw.store(sl, tid, st[r % D]);
+            sl = (sl + 1 == (unsigned)NWB) ? 0u : sl + 1;
+        }
+        if (r + D < R2) mk[r % D] = dia_mask_load(a.dmask, fb + (int64_t)(r + D) * CH_BS);
+        if (r + D + 1 < R2) st[r % D] = xw.load(fb + hs + (int64_t)(r + D) * CH_BS);
+        ch_lds_barrier();        // block hi + 1 + r is in the ring; nobody reads row r's oldest block any more
+        asm volatile("" : "+v"(fb), "+v"(tb) : : "memory");
+    }
+}
+
 // The operator's form is chosen by ONE wave-uniform branch (a kernel argument) around two straight-line copies of the
 // row loop, never inside it: no new kernel symbols, and the unrolled loop itself stays free of control flow.
 template <int R2, int FND, int RIF = KH_RIF, class Put>
@@ -1041,6 +1191,9 @@ __global__ __launch_bounds__(CH_BS) void k_mgs_chain(ChainArgs a) {
 #ifndef KH_CH_LDS_EARLY
 #define KH_CH_LDS_EARLY 0
 #endif
+#ifndef KH_XWIN_AHEAD
+#define KH_XWIN_AHEAD 4   // blocks of x (and rows of masks) in flight ahead of the row in work
+#endif
 template <int R2, bool CPLX = false>
 struct ChainShapeLds {
     // 5 rows per batch for R2 = 40, like the plain kernel (the complex instantiation spills 36 registers
@@ -1061,6 +1214,8 @@ struct ChainShapeLds {
     static_assert((NB % 2) == 0 && NG >= 0 && (NG % 2) == 0, "ring parity must reset every phase");
     static_assert(WL <= LROWS && LROWS <= R2 - PB, "the prologue's rows of w borrow parked rows; the last batch stays in the ring");
     static constexpr size_t LDS_BYTES = (size_t)LROWS * CH_BS * sizeof(double2);
+    // blocks of the prologue's x window (chain_apply_banded_xwin): the parked rows that the prologue's rows of w leave free
+    static constexpr int XWIN_BLOCKS = LROWS - WL;
     // static LDS of k_mgs_chain_lds: smd[4 * CH_BS / 64] doubles, smu[2 * CH_GMAX] words, slead
     static constexpr size_t STATIC_LDS = 4 * (CH_BS / 64) * sizeof(double) + 2 * CH_GMAX * sizeof(unsigned) + sizeof(int);
     static_assert(LDS_BYTES + STATIC_LDS <= 160 * 1024, "a CU has 160 KB of LDS");
@@ -1107,6 +1262,15 @@ __global__ __launch_bounds__(CH_BS) void k_mgs_chain_lds(ChainArgs a) {
     double2 ring[2][PB];
     if constexpr (FND > 0 && CPLX) {
         chain_apply_banded_z<R2, FND>(a, first, [&](int r, double s0, double s1) { W_PUT(r, make_double2(s0, s1)); });
+    } else if constexpr (FND > 0 && !XR) {
+        // x through the LDS window (the parked rows behind the prologue's WL rows of w: idle until the first link's dot
+        // phase, and the window's last barrier is behind its last read) or through gathers: one wave-uniform branch
+        constexpr int NWB = ChainShapeLds<R2, CPLX>::XWIN_BLOCKS;
+        if (a.xwin)
+            chain_apply_banded_xwin<R2, FND, NWB, KH_XWIN_AHEAD>(a, first, reinterpret_cast<double*>(vlds + WL * CH_BS),
+                                                                 [&](int r, double s0, double s1) { W_PUT(r, make_double2(s0, s1)); });
+        else
+            chain_apply_banded<R2, FND>(a, first, [&](int r, double s0, double s1) { W_PUT(r, make_double2(s0, s1)); });
     } else if constexpr (FND > 0) {
         chain_apply_banded<R2, FND>(a, first, [&](int r, double s0, double s1) { W_PUT(r, make_double2(s0, s1)); });
     } else {

@@ -110,6 +110,7 @@ int chain_blk2_step(kh_ctx ctx, kh_vec V, const double* w, int64_t wld, int64_t 
         ctx->n_blk_rebuild += 1;
     }
     ChainArgs a;
+    a.xwin = 0;
     memset(&a, 0, sizeof(a));
     a.n2 = (n + 1) >> 1;
     a.chunk2 = chunk2;

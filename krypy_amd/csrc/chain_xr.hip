@@ -115,6 +115,7 @@ int chain_xr_step(kh_ctx ctx, kh_vec V, const double* w, int64_t wld, int64_t k,
     const int64_t need_ld = (int64_t)G * chunk2 * 2;
     const bool padded = V->ld >= need_ld && wld >= need_ld;
     ChainArgs a;
+    a.xwin = 0;
     memset(&a, 0, sizeof(a));
     a.n2 = (n + 1) >> 1;
     a.chunk2 = chunk2;

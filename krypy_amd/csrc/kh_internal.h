@@ -134,6 +134,9 @@ struct kh_ctx_s {
     double* gram_part = nullptr;     // [256][KH_GRAM_NB] workgroup partials of k_gram_mfma (allocated at first use)
     int64_t n_zspmv_dia = 0;         // products of a banded complex operator through its diagonal-major copy (zpath.h: k_zspmv_dia)
     int64_t n_dia_mask = 0;          // launches that read a constant-coefficient banded operator's presence masks (dmask)
+    int chain_xwin = 1;              // KRYPY_AMD_CHAIN_XWIN: k_mgs_chain_lds' mask-form prologue reads x through an LDS window where the
+                                     // band fits (chain.h: chain_apply_banded_xwin) instead of through clamped gathers
+    int64_t n_chain_xwin = 0;        // launches that did
     int chain_xr = 1;
     int chain_xr_cus = 0;            // tests: the compute units the shape is chosen for (0: all; two processes share one device)
     int64_t n_chain_xr = 0;

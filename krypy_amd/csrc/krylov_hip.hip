@@ -752,6 +752,7 @@ int try_chain(kh_ctx ctx, kh_vec V, kh_vec B, const double* w, int64_t wld, cons
                         wld >= need_ld;
     KH_TRY(chain_epoch_check(ctx));
     ChainArgs a;
+    a.xwin = 0;
     a.n2 = n2;
     a.chunk2 = chunk2;
     a.V = V->d;
@@ -1010,6 +1011,11 @@ int try_chain(kh_ctx ctx, kh_vec V, kh_vec B, const double* w, int64_t wld, cons
     }
     a.onex_G = 0;
     for (int attempt = 0; attempt < 2; ++attempt) {
+        // k_mgs_chain_lds, mask form: x through the prologue's LDS window when a row's band and the block staged beside it
+        // fit the parked rows the prologue leaves free (all or nothing per launch; x must start a 16-byte row)
+        a.xwin = (fused && !cplx && use_lds && !use_pf && ctx->chain_xwin && a.dmask != nullptr && r2 >= 16 && r2 <= 40 &&
+                  (reinterpret_cast<uintptr_t>(a.xk) & 15u) == 0 &&
+                  xwin_fits(a.offs, a.offs.nd, r2 == 40 ? ChainShapeLds<40>::XWIN_BLOCKS : ChainShapeLds<32>::XWIN_BLOCKS)) ? 1 : 0;
         if (fused) {
 #define KH_FUSED(R, D)                                                                                   \
     (use_lds ? (use_pf ? launch_chain_pf<R, false, false, D>(ctx, G, a) : launch_chain_lds<R, false, false, D>(ctx, G, a)) \
@@ -1088,6 +1094,7 @@ int try_chain(kh_ctx ctx, kh_vec V, kh_vec B, const double* w, int64_t wld, cons
     ctx->n_chain_pf += use_pf ? 1 : 0;
     ctx->n_chain_fused += fused ? 1 : 0;
     ctx->n_dia_mask += (fused && a.dmask != nullptr) ? 1 : 0;
+    ctx->n_chain_xwin += a.xwin;
     ctx->chain_epoch += (unsigned)(a.ncol * a.sweeps + 1);   // one grid reduction per link (complex: both parts in it) + the norm
     if (hpin == nullptr)      // (otherwise workgroup 0 has written the error word to the pinned slot itself)
         KH_HIP(hipMemcpyAsync(ctx->chain_err_pin[slot], ctx->chain_err, sizeof(int), hipMemcpyDeviceToHost,
@@ -1467,6 +1474,8 @@ int kh_ctx_create(int device, kh_ctx* out) {
         ctx->chain_configured = ctx->chain_enabled;
         e = getenv("KRYPY_AMD_CHAIN_SPMV");
         ctx->chain_spmv = (e == nullptr) ? 1 : atoi(e);
+        e = getenv("KRYPY_AMD_CHAIN_XWIN");
+        ctx->chain_xwin = (e == nullptr) ? 1 : (atoi(e) != 0);
         e = getenv("KRYPY_AMD_CHAIN_LDS");
         ctx->chain_lds = (e == nullptr) ? 1 : atoi(e);
         e = getenv("KRYPY_AMD_CHAIN_PF");
@@ -1613,6 +1622,7 @@ int kh_ctx_set(kh_ctx ctx, const char* key, int64_t value) {
     else if (!strcmp(key, "chain_lds")) ctx->chain_lds = value != 0;
     else if (!strcmp(key, "chain_pf")) ctx->chain_pf = (int)value;
     else if (!strcmp(key, "chain_spmv")) ctx->chain_spmv = value != 0;
+    else if (!strcmp(key, "chain_xwin")) ctx->chain_xwin = value != 0;
     else if (!strcmp(key, "chain_fault")) ctx->chain_fault = value != 0;
     else if (!strcmp(key, "spmv_split")) ctx->spmv_split = value != 0;
     else if (!strcmp(key, "halo_loopback")) ctx->halo_loopback = value != 0;
@@ -1693,6 +1703,8 @@ int kh_ctx_get(kh_ctx ctx, const char* key, int64_t* value) {
     else if (!strcmp(key, "chain_pf")) *value = ctx->chain_pf;
     else if (!strcmp(key, "n_chain_pf")) *value = ctx->n_chain_pf;
     else if (!strcmp(key, "chain_spmv")) *value = ctx->chain_spmv;
+    else if (!strcmp(key, "chain_xwin")) *value = ctx->chain_xwin;
+    else if (!strcmp(key, "n_chain_xwin")) *value = ctx->n_chain_xwin;
     else if (!strcmp(key, "n_spmm")) *value = ctx->n_spmm;
     else if (!strcmp(key, "spmv_split")) *value = ctx->spmv_split;
     else if (!strcmp(key, "n_spmv_split")) *value = ctx->n_spmv_split;

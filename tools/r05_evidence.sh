@@ -118,7 +118,7 @@ fallback)
   run "KRYPY_AMD_CG_STEP=0 KRYPY_AMD_SPMV_SPLIT=0 KRYPY_AMD_PROJ_PANEL=0 KRYPY_AMD_CGS_REVERSE=0 KRYPY_AMD_BLK_NX=0 KRYPY_AMD_XR=0 KRYPY_AMD_CHAIN_BLK2=0 KRYPY_AMD_XH=0 KRYPY_AMD_SPMV_WIN=0 KRYPY_AMD_BLK2_ONE=0"
   run "KRYPY_AMD_BLK2_CW=0"
   run "KRYPY_AMD_BLK2_CW=2"
-  run "KRYPY_AMD_CHAIN_XR=0 KRYPY_AMD_CHAIN_LONG=0 KRYPY_AMD_GRAM_MFMA=0"
+  run "KRYPY_AMD_CHAIN_XR=0 KRYPY_AMD_CHAIN_LONG=0 KRYPY_AMD_GRAM_MFMA=0 KRYPY_AMD_CHAIN_XWIN=0"
   grep -c "^FAILED" gpurun_out/ev/fallback.log | sed 's/^/numeric FAILED lines in all switch sets: /' >> gpurun_out/ev/fallback.log
   cat gpurun_out/ev/fallback.log
   ;;
