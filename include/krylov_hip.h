@@ -38,6 +38,7 @@ typedef struct kh_ctx_s* kh_ctx;
 typedef struct kh_mat_s* kh_mat;
 typedef struct kh_vec_s* kh_vec;
 typedef struct kh_proj_s* kh_proj;
+typedef struct kh_tri_s* kh_tri;
 
 typedef enum {
     KH_OK = 0,
@@ -457,6 +458,37 @@ int kh_zminres_update(kh_ctx ctx, kh_vec V, int64_t k, kh_vec Wk, int slot, cons
 int kh_zcg_step(kh_ctx ctx, kh_mat A, kh_mat Md, kh_vec Pd, int64_t pcol, kh_vec AP, int64_t apcol, kh_vec YK,
                 int64_t ycol, kh_vec R, int64_t rcol, kh_vec Z, int64_t zcol, int first, double omega, double rho,
                 double* out);
+
+/* ---- sparse triangular solves (incomplete-factorisation / Gauss-Seidel preconditioners) ------------------------------ */
+/* All five entry points serve the M, Ml, Mr hooks of krypy/linsys.py (and ip_B): the factors of an ILU / IC / SSOR
+ * preconditioner applied on the device.  No reference counterpart - the reference calls the user's function on host arrays.
+ * The operator is T^{-1} for a sparse triangular T, by level scheduling (krypy_amd/csrc/tri.h, tri.hip): one thread per row,
+ * s = b_i; s -= t_ij x_j in ascending column order (multiply and subtract rounded separately); x_i = s / t_ii - the bits of the
+ * sequential row-by-row substitution.  A handle type of its own: a kh_tri is not a kh_mat and kh_apply never sees one. */
+/* M / Ml / Mr hooks, no reference counterpart.  T as CSR with SORTED, duplicate-free int32 indices; lower != 0: lower triangle;
+ * unit_diag != 0: the diagonal is 1 and a stored diagonal entry is ignored, else every row needs a non-zero diagonal entry.
+ * The level analysis runs on the host here, O(nnz).  kh_ctx_set "tri_narrow_rows" (default 1024; read HERE): consecutive levels
+ * of at most that many rows share one launch of one workgroup, every other level is one launch of its own.  KH_ERR_ARG: an
+ * entry on the wrong side of the diagonal, a missing / zero diagonal, unsorted or duplicate indices; KH_ERR_NOMEM: an
+ * allocation failed; KH_ERR_UNSUPPORTED: the context has a communicator (sharded triangular solves do not exist). */
+int kh_tri_create(kh_ctx ctx, int64_t n, int64_t nnz, const int32_t* indptr, const int32_t* indices, const double* data,
+                  int lower, int unit_diag, kh_tri* out);
+/* M / Ml / Mr hooks with complex data, no reference counterpart: the same with (re, im) pairs; NumPy's complex product and
+ * quotient (Smith's formula), as kh_zcg_step. */
+int kh_ztri_create(kh_ctx ctx, int64_t n, int64_t nnz, const int32_t* indptr, const int32_t* indices, const double* data_re_im,
+                   int lower, int unit_diag, kh_tri* out);
+/* M / Ml / Mr hooks, no reference counterpart: releases the device copy (waits for the stream first). */
+int kh_tri_free(kh_tri t);
+/* M / Ml / Mr hooks, no reference counterpart.  Y[:, ycol + c] = T^{-1} X[:, xcol + c], c < ncols (one column after the other).
+ * X and Y may be the same columns (in place); ranges of one block that overlap without being identical are KH_ERR_ARG (a
+ * column would overwrite a later right-hand side).  Rows [n, ld) of Y are not written.  Blocks of a complex handle are the (re, im) views of
+ * length 2 n.  KH_ERR_ARG when the length of the blocks does not match (also: a real handle on complex blocks or the reverse).
+ * Counters (kh_ctx_get): "n_tri_solve" columns solved, "n_tri_wide" / "n_tri_narrow" launches of the two kinds. */
+int kh_tri_solve(kh_ctx ctx, kh_tri t, kh_vec X, int64_t xcol, kh_vec Y, int64_t ycol, int64_t ncols);
+/* M / Ml / Mr hooks, no reference counterpart (diagnostics of the plan): out = n, nnz, levels, wide launches per solve, narrow
+ * launches per solve, stored off-diagonal slots including padding, rows of the widest level, off-diagonal entries of the
+ * longest row. */
+int kh_tri_info(kh_tri t, int64_t out[8]);
 
 /* ---- measurement ----------------------------------------------------------------------- */
 /* bench.py's roofline numbers: average duration (ms) of `reps` back-to-back launches of one hot

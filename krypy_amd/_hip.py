@@ -14,7 +14,7 @@ import os
 
 import numpy
 
-__all__ = ["BackendError", "Context", "DeviceVectors", "DeviceMatrix", "get_context",
+__all__ = ["BackendError", "Context", "DeviceVectors", "DeviceMatrix", "DeviceTriangular", "get_context",
            "library_path", "load_library", "GS_MGS", "GS_CGS"]
 
 GS_MGS = 0
@@ -108,6 +108,12 @@ _SIGNATURES = {
     "kh_house_step_end": [_H, _INT, _I64, _c_double_p],
     "kh_zhouse_step_begin": [_H, _H, _H, _H, _H, _I64, _I64, _INT],
     "kh_zhouse_step_end": [_H, _INT, _I64, _c_double_p],
+    # sparse triangular solves (csrc/tri.hip): the factors of ILU / IC / SSOR preconditioners
+    "kh_tri_create": [_H, _I64, _I64, _c_int32_p, _c_int32_p, _c_double_p, _INT, _INT, ctypes.POINTER(_H)],
+    "kh_ztri_create": [_H, _I64, _I64, _c_int32_p, _c_int32_p, _c_double_p, _INT, _INT, ctypes.POINTER(_H)],
+    "kh_tri_free": [_H],
+    "kh_tri_solve": [_H, _H, _H, _I64, _H, _I64, _I64],
+    "kh_tri_info": [_H, _c_int64_p],
     "kh_residual": [_H, _H, _H, _I64, _H, _I64, _H, _I64, _c_double_p],
     "kh_gmres_cycle": [_H, _H, _H, _H, _H, _H, _I64, _I64, _I64, _INT, _INT, _c_int64_p, _D, _D, _c_double_p, _I64,
                        _c_double_p, _I64, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_int64_p,
@@ -277,6 +283,30 @@ class DeviceProjector(object):
         try:
             if self.handle is not None and self.ctx._alive:
                 self.ctx._lib.kh_proj_free(self.handle)
+        except Exception:
+            pass
+        self.handle = None
+
+
+class DeviceTriangular(object):
+    """The inverse of a sparse triangular matrix on the device (``kh_tri``): level-scheduled substitution."""
+
+    def __init__(self, ctx, handle, shape, nnz, dtype, lower, unit_diagonal):
+        self.ctx, self.handle, self.shape, self.nnz = ctx, handle, shape, nnz
+        self.dtype = numpy.dtype(dtype)
+        self.lower, self.unit_diagonal = bool(lower), bool(unit_diagonal)
+
+    def info(self):
+        """The launch plan (``kh_tri_info``)."""
+        buf = (ctypes.c_int64 * 8)()
+        _check(self.ctx._lib, self.ctx._lib.kh_tri_info(self.handle, buf), "kh_tri_info")
+        return dict(n=buf[0], nnz=buf[1], levels=buf[2], wide_launches=buf[3], narrow_launches=buf[4], slots=buf[5],
+                    widest_level=buf[6], longest_row=buf[7])
+
+    def __del__(self):
+        try:
+            if self.handle is not None and self.ctx._alive:
+                self.ctx._lib.kh_tri_free(self.handle)
         except Exception:
             pass
         self.handle = None
@@ -682,6 +712,29 @@ class Context(object):
         fn = self._lib.kh_zdiag_upload if dt == _C128 else self._lib.kh_diag_upload
         _check(self._lib, fn(self._h, d.size, _dptr(d), ctypes.byref(h)), "kh_diag_upload")
         return DeviceMatrix(self, h, "diag", (d.size, d.size), d.size, dt)
+
+    def tri(self, T, lower, unit_diagonal=False, dtype=None):
+        """``T^{-1}`` for a triangular SciPy CSR matrix with sorted, duplicate-free indices (``kh_tri_create`` /
+        ``kh_ztri_create``); the level analysis runs here, once."""
+        indptr = numpy.ascontiguousarray(T.indptr, dtype=numpy.int32)
+        indices = numpy.ascontiguousarray(T.indices, dtype=numpy.int32)
+        dt = _block_dtype(T.dtype if dtype is None else numpy.result_type(T.dtype, dtype))
+        data = numpy.ascontiguousarray(T.data, dtype=dt)
+        if T.shape[0] != T.shape[1]:
+            raise BackendError("tri: a square matrix expected, got %s" % (T.shape,))
+        h = _H()
+        fn = self._lib.kh_ztri_create if dt == _C128 else self._lib.kh_tri_create
+        _check(self._lib, self._with_memory(lambda: fn(
+            self._h, T.shape[0], data.size, indptr.ctypes.data_as(_c_int32_p), indices.ctypes.data_as(_c_int32_p),
+            _dptr(data), 1 if lower else 0, 1 if unit_diagonal else 0, ctypes.byref(h))), "kh_tri_create")
+        return DeviceTriangular(self, h, T.shape, data.size, dt, lower, unit_diagonal)
+
+    def tri_solve(self, t, X, xcol, Y, ycol, ncols=1):
+        """``Y[:, ycol:ycol+ncols] = T^{-1} X[:, xcol:xcol+ncols]`` (``kh_tri_solve``); X and Y may be the same columns."""
+        if (t.dtype == _C128) != _same_dtype("tri_solve", X, Y):
+            raise BackendError("tri_solve: %s operator on %s blocks" % (t.dtype, X.dtype))
+        _check(self._lib, self._lib.kh_tri_solve(self._h, t.handle, X.handle, xcol, Y.handle, ycol, ncols),
+               "kh_tri_solve")
 
     # ---- numerics (each is one C entry point; complex blocks go to the kh_z* twin) ----
     def apply(self, A, X, xcol, Y, ycol, ncols=1):

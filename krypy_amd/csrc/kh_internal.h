@@ -94,6 +94,9 @@ struct kh_ctx_s {
     int64_t n_zhouse_chain = 0;      // launches of the complex step (k_zhouse_chain); switch, budget and recoveries are shared
     int64_t house_refused_n = -1;    // vector length whose launch the runtime refused (occupancy)
     int64_t zhouse_refused_n = -1;   // ... of the complex kernel (the length of the (re, im) view)
+    // sparse triangular solves (tri.hip): levels of at most tri_narrow_rows rows share a one-workgroup launch (read by kh_tri_create)
+    int64_t tri_narrow_rows = 1024;
+    int64_t n_tri_solve = 0, n_tri_wide = 0, n_tri_narrow = 0;   // columns solved; launches of k_tri_wide / k_tri_narrow
     int64_t n_spmm = 0;     // panel applications of a CSR operator that streamed the matrix once
     int chain_spmv = 1;     // banded operators: w = A v_k in the chain kernel's prologue (KRYPY_AMD_CHAIN_SPMV)
     int chain_pf = 1;       // ... and keep HBM busy through the update phase (k_mgs_chain_pf; KRYPY_AMD_CHAIN_PF)

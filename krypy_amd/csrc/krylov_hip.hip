@@ -1685,6 +1685,10 @@ int kh_ctx_set(kh_ctx ctx, const char* key, int64_t value) {
         ctx->house_refused_n = -1;
         ctx->zhouse_refused_n = -1;
     }
+    else if (!strcmp(key, "tri_narrow_rows")) {       // kh_tri_create reads it: 0 = every level a launch of its own
+        KH_ARG(value >= 0, "kh_ctx_set: tri_narrow_rows < 0");
+        ctx->tri_narrow_rows = value;
+    }
     else if (!strcmp(key, "chain_epoch")) ctx->chain_epoch = (unsigned)value;      // tests: bring the epoch counter of the grid-wide sums near its wrap
     else if (!strcmp(key, "chain_debug")) ctx->chain_debug = (int)value;    // measurement: phases switched off (garbage results)
     else return fail(KH_ERR_ARG, "kh_ctx_set: unknown key '%s'", key);
@@ -1760,6 +1764,10 @@ int kh_ctx_get(kh_ctx ctx, const char* key, int64_t* value) {
     else if (!strcmp(key, "n_house_chain")) *value = ctx->n_house_chain;
     else if (!strcmp(key, "n_zhouse_chain")) *value = ctx->n_zhouse_chain;
     else if (!strcmp(key, "n_house_recovered")) *value = ctx->n_house_recovered;
+    else if (!strcmp(key, "tri_narrow_rows")) *value = ctx->tri_narrow_rows;
+    else if (!strcmp(key, "n_tri_solve")) *value = ctx->n_tri_solve;
+    else if (!strcmp(key, "n_tri_wide")) *value = ctx->n_tri_wide;
+    else if (!strcmp(key, "n_tri_narrow")) *value = ctx->n_tri_narrow;
     else if (!strcmp(key, "chain_epoch")) *value = ctx->chain_epoch;
     else if (!strcmp(key, "n_epoch_wraps")) *value = ctx->n_epoch_wraps;
     else return fail(KH_ERR_ARG, "kh_ctx_get: unknown key '%s'", key);

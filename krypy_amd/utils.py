@@ -31,7 +31,7 @@ __all__ = [
     "ZeroLinearOperator", "Projection", "arnoldi", "arnoldi_res", "find_common_dtype",
     "get_linearoperator", "inner", "ip_euclid", "norm", "norm_squared", "orthonormality", "qr",
     "shape_vec", "shape_vecs", "DVec", "Timer", "Timings", "TimedLinearOperator", "ritz",
-    "hegedus", "angles",
+    "hegedus", "angles", "TriangularSolveOperator", "ilu_operator",
 ]
 
 
@@ -915,6 +915,101 @@ class DeviceOperator(MatrixLinearOperator):
 
     def __repr__(self):
         return "<DeviceOperator %dx%d %s on the device>" % (self.shape[0], self.shape[1], self.dtype)
+
+
+class TriangularSolveOperator(LinearOperator):
+    """``T^{-1}`` for a sparse triangular matrix ``T``, applied on the device by level-scheduled substitution
+    (``Context.tri`` / ``tri_solve``): the factor of an incomplete factorisation or a Gauss-Seidel sweep as ``M``, ``Ml``,
+    ``Mr`` or ``ip_B`` of a solver, without a trip over the host.  The reference has no counterpart (it takes any callable).
+
+    ``lower=None`` infers the side from the structure; ``unit_diagonal=True`` takes the diagonal as 1 whatever is stored.
+    The result is that of the row-by-row substitution ``s = b_i; s -= t_ij x_j`` (ascending ``j``), ``x_i = s / t_ii``.
+    ``_device_matrix()`` stays None: the solvers treat it as an external operator, applied once per step."""
+
+    def __init__(self, T, lower=None, unit_diagonal=False):
+        if not _is_sparse(T):
+            T = numpy.asarray(T)
+            if T.ndim != 2:
+                raise ArgumentError("a matrix expected, got an array of shape %s" % (T.shape,))
+        T = scipy.sparse.csr_matrix(T, copy=True)
+        if T.shape[0] != T.shape[1]:
+            raise ArgumentError("a square triangular matrix expected, got shape %s" % (T.shape,))
+        T.sum_duplicates()
+        T.sort_indices()
+        if T.dtype not in (numpy.dtype(numpy.float64), numpy.dtype(numpy.complex128)):
+            T = T.astype(_bdt(T.dtype))          # the device works in fp64 / c128 and the operator says so
+        C = T.tocoo()
+        below, above = bool(numpy.any(C.row > C.col)), bool(numpy.any(C.row < C.col))
+        if lower is None:
+            if below and above:
+                raise ArgumentError("T is not triangular: entries on both sides of the diagonal")
+            lower = not above
+        elif (above if lower else below):
+            raise ArgumentError("T has entries %s the diagonal, lower=%r" % ("above" if lower else "below", bool(lower)))
+        if not unit_diagonal and numpy.any(T.diagonal() == 0):
+            raise ArgumentError("T has a zero or missing diagonal entry in row %d (unit_diagonal=False)"
+                                % int(numpy.flatnonzero(T.diagonal() == 0)[0]))
+        super(TriangularSolveOperator, self).__init__(T.shape, T.dtype, self._dot, self._dot_adj)
+        self._T, self.lower, self.unit_diagonal = T, bool(lower), bool(unit_diagonal)
+        self._dtris = {}
+        self._adj_op = None
+
+    def _device_tri(self, ctx, dtype=None):
+        """Device image for blocks of ``dtype``: a real T is created a second time as c128 when it meets complex vectors."""
+        dt = _bdt(self.dtype, dtype)
+        key = (id(ctx), dt.kind)
+        t = self._dtris.get(key)
+        if t is None:
+            t = self._dtris[key] = ctx.tri(self._T, self.lower, self.unit_diagonal, dtype=dt)
+        return t
+
+    def _apply_dev(self, X, xcol, Y, ycol, ncols=1):
+        if _is_c(self.dtype) and not _is_c(X.dtype):
+            raise LinearOperatorError("complex triangular matrix applied to a real device block")
+        X.ctx.tri_solve(self._device_tri(X.ctx, X.dtype), X, xcol, Y, ycol, ncols)
+
+    def _dot(self, X):
+        X = numpy.asarray(X)
+        ctx = _hip.get_context()
+        dt = _bdt(self.dtype, X.dtype)
+        Xd = ctx.upload(X, dtype=dt)
+        Yd = ctx.alloc(self.shape[0], X.shape[1], dtype=dt)
+        self._apply_dev(Xd, 0, Yd, 0, X.shape[1])
+        return numpy.ascontiguousarray(Yd.download())
+
+    @property
+    def adj(self):
+        """``(T^H)^{-1}``: the triangular solve with the conjugate transpose, the other triangle."""
+        if self._adj_op is None:
+            self._adj_op = TriangularSolveOperator(self._T.conj().T, lower=not self.lower, unit_diagonal=self.unit_diagonal)
+            self._adj_op._adj_op = self
+        return self._adj_op
+
+    def _dot_adj(self, X):
+        return self.adj._dot(X)
+
+    def __repr__(self):
+        return "<%dx%d TriangularSolveOperator (%s%s) with dtype=%s>" % (
+            self.shape[0], self.shape[1], "lower" if self.lower else "upper", ", unit diagonal" if self.unit_diagonal else "",
+            self.dtype)
+
+
+def ilu_operator(ilu):
+    """The solve of a sparse LU / incomplete LU factorisation as a device operator: ``ilu`` is any object with ``L``
+    (unit lower), ``U`` (upper), ``perm_r`` and ``perm_c`` - what ``scipy.sparse.linalg.spilu`` / ``splu`` return.
+    ``ilu.solve(b)`` is ``y[perm_r] = b; z = U^{-1} L^{-1} y; x = z[perm_c]``; the operator is ``Pc * Uinv * Linv * Pr``
+    with the two triangular solves on the device and the permutations as CSR matrices of ones (left out when they are the
+    identity)."""
+    L, U = ilu.L, ilu.U
+    n = L.shape[0]
+    ar = numpy.arange(n)
+    op = TriangularSolveOperator(U, lower=False) * TriangularSolveOperator(L, lower=True, unit_diagonal=True)
+    perm_r, perm_c = numpy.asarray(ilu.perm_r), numpy.asarray(ilu.perm_c)
+    if not numpy.array_equal(perm_r, ar):
+        op = op * MatrixLinearOperator(scipy.sparse.csr_matrix((numpy.ones(n), (perm_r, ar)), shape=(n, n)))
+    if not numpy.array_equal(perm_c, ar):
+        op = MatrixLinearOperator(scipy.sparse.csr_matrix((numpy.ones(n), (ar, perm_c)), shape=(n, n))) * op
+    return op
 
 
 class Timer(list):
