@@ -29,7 +29,7 @@ CHAIN_LINKS = 64   # kh_bench_kernel runs the chain over 16 columns x 4 sweeps
 
 _SOURCES = ("chain.h", "kernels.h", "krylov_hip.hip", "kh_internal.h", "zpath.h", "comm.hip", "lanczos.h", "chain_blk.h",
             "chain_blk.hip", "proj_reg.h", "proj_reg.hip", "xr.hip", "xr_dev.h", "chain_blk2.h", "chain_blk2.hip", "chain_xr.hip", "chain_long.h", "cycles.hip",
-            "bench_abi.hip", "krylov_steps.h")
+            "bench_abi.hip", "krylov_steps.h", "chain_launch.hip", "kh_launch.h")
 
 
 def source_stamp():

@@ -14,6 +14,18 @@
 
 using namespace kh;
 
+// the Gram-Schmidt chain of a measurement: w against columns 0 .. k of V, `sweeps` times, the H column into slot 0's device buffer
+static int bench_chain(kh_ctx ctx, kh_vec V, const double* w, int64_t wld, int64_t k, int sweeps) {
+    ChainStep s;
+    s.V = s.B = V;
+    s.w = w;
+    s.wld = wld;
+    s.k = k;
+    s.sweeps = sweeps;
+    s.hdev = ctx->hslot_dev[0];
+    return try_chain(ctx, s);
+}
+
 extern "C" {
 
 // Timing harness for bench.py: `reps` back-to-back launches of one hot kernel between two HIP
@@ -74,8 +86,7 @@ int kh_bench_kernel(kh_ctx ctx, int which, kh_vec V, kh_vec W, int reps, double*
                 // the register-resident chain over 16 columns x 4 sweeps = 64 links per launch
                 ctx->chain_debug = which - 5;
                 KH_HIP(hipMemsetAsync(ctx->hslot_dev[0], 0, sizeof(double) * 64, ctx->stream));
-                const int rc = try_chain(ctx, V, V, w, W->ld, nullptr, nullptr, 15, 0, 4, false, 0.0,
-                                         nullptr, ctx->hslot_dev[0], 0);
+                const int rc = bench_chain(ctx, V, w, W->ld, 15, 4);
                 ctx->chain_debug = 0;
                 if (rc != 1) return fail(KH_ERR_UNSUPPORTED, "kh_bench_kernel: chain kernel not eligible");
                 break;
@@ -92,8 +103,7 @@ int kh_bench_kernel(kh_ctx ctx, int which, kh_vec V, kh_vec W, int reps, double*
                 ctx->blk_V = V;
                 ctx->blk_next = 63;
                 const int64_t nb0 = ctx->n_chain_blk;
-                const int rc = try_chain(ctx, V, V, w, W->ld, nullptr, nullptr, 63, 0, 1, false, 0.0, nullptr,
-                                         ctx->hslot_dev[0], 0);
+                const int rc = bench_chain(ctx, V, w, W->ld, 63, 1);
                 ctx->chain_debug = 0;
                 ctx->blk_next = -1;
                 if (rc != 1 || ctx->n_chain_blk == nb0) return fail(KH_ERR_UNSUPPORTED, "kh_bench_kernel: blocked chain kernel not eligible");
@@ -102,8 +112,7 @@ int kh_bench_kernel(kh_ctx ctx, int which, kh_vec V, kh_vec W, int reps, double*
             case 24: {     // ... and the per-column kernel on the same 64 columns
                 const int keep = ctx->chain_blk;
                 ctx->chain_blk = 0;
-                const int rc = try_chain(ctx, V, V, w, W->ld, nullptr, nullptr, 63, 0, 1, false, 0.0, nullptr,
-                                         ctx->hslot_dev[0], 0);
+                const int rc = bench_chain(ctx, V, w, W->ld, 63, 1);
                 ctx->chain_blk = keep;
                 if (rc != 1) return fail(KH_ERR_UNSUPPORTED, "kh_bench_kernel: chain kernel not eligible");
                 break;
@@ -209,8 +218,7 @@ int kh_chain_trace(kh_ctx ctx, kh_vec V, kh_vec W, unsigned long long* out, int6
     KH_HIP(hipMemset(dev, 0, words * sizeof(unsigned long long)));
     for (int rep = 0; rep < 4; ++rep) {
         ctx->chain_trace = (rep == 3) ? dev : nullptr;
-        const int rc = try_chain(ctx, V, V, W->col(0), W->ld, nullptr, nullptr, 15, 0, 4, false, 0.0, nullptr,
-                                 ctx->hslot_dev[0], 0);
+        const int rc = bench_chain(ctx, V, W->col(0), W->ld, 15, 4);
         ctx->chain_trace = nullptr;
         if (rc != 1) {
             (void)hipFree(dev);

@@ -4,6 +4,7 @@
 
 #include "kh_internal.h"
 #include "chain_blk.h"
+#include "kh_launch.h"
 
 namespace kh {
 
@@ -36,24 +37,20 @@ void chain_blk_free(kh_ctx ctx) {
 }
 
 template <int R2, bool MASKED, int FND, bool ONEX, int DBG = 0>
-static hipError_t launch_blk(kh_ctx ctx, int G, ChainArgs& a, BlkBufs bf) {
-    static int blocks_per_cu = -1;
-    auto kern = k_mgs_chain_blk<R2, BLK_BC, BLK_NSLOT, MASKED, FND, ONEX, DBG>;
-    if (blocks_per_cu < 0) {
-        int nb = 0;
-        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, CH_BS + 64, 0);
-        if (e != hipSuccess) return e;
-        blocks_per_cu = nb;
-    }
-    if ((int64_t)blocks_per_cu * (ONEX ? ctx->ncu / 8 : ctx->ncu) < G) return hipErrorCooperativeLaunchTooLarge;
+static hipError_t launch_blk(kh_ctx ctx, int G, const ChainArgs& a, BlkBufs bf) {
+    constexpr auto kern = k_mgs_chain_blk<R2, BLK_BC, BLK_NSLOT, MASKED, FND, ONEX, DBG>;
+    constexpr int block = CH_BS + 64;      // + the communication wave
+    bf.nx = 0;
+    if constexpr (ONEX) return launch_resident<kern>(ctx, G, ResidentShape::one_xcd(ctx, block, G, 0), a, bf);
+    int per_cu = 0;
+    const hipError_t e = resident_per_cu<kern>(ctx, block, 0, &per_cu);
+    if (e != hipSuccess) return e;
     // workgroups WITHOUT rows in front of the G with rows (chain_blk.h, BlkBufs::nx): when the chip has room for them, and
     // from as many workgroups on as the two-level exchange takes (fewer: the leaders gather everything themselves)
-    bf.nx = 0;
-    if (!ONEX && DBG == 0 && ctx->blk_nx > 0 && (int64_t)blocks_per_cu * ctx->ncu >= G + ctx->blk_nx && G + ctx->blk_nx <= CH_GMAX / 2)
+    if (DBG == 0 && ctx->blk_nx > 0 && (int64_t)per_cu * ctx->ncu >= G + ctx->blk_nx && G + ctx->blk_nx <= CH_GMAX / 2)
         bf.nx = ctx->blk_nx;
     if (bf.nx > 0) ctx->n_blk_rowless += 1;
-    hipLaunchKernelGGL(kern, dim3(ONEX ? 8 * G + 8 : G + bf.nx), dim3(CH_BS + 64), 0, ctx->stream, a, bf);
-    return hipGetLastError();
+    return launch_resident<kern>(ctx, G, ResidentShape{block, G + bf.nx, ctx->ncu, 0}, a, bf);
 }
 
 // The Gram table (device): row j = <v_m, v_j> for the BLK_BC columns of the block before j's and the columns m < j of j's block.
@@ -73,7 +70,7 @@ bool chain_blk_shape_ok(int r2, int G, const ChainArgs& a, int fnd) {
 // it consumes).  hipErrorInvalidValue: no instantiation for this shape.
 // The Gram table belongs to ONE Arnoldi sequence at a time: (ctx->blk_V, ctx->blk_next) name the basis block and the
 // step whose launch finds rows 0 .. k of the table valid - the caller has checked that, or has rebuilt the rows
-// (krylov_hip.hip: blk_table_ready).  The launch leaves row k + 1 behind.
+// (chain_launch.hip: chain_stage_ring).  The launch leaves row k + 1 behind.
 hipError_t chain_blk_launch(kh_ctx ctx, int r2, int G, bool onex, bool padded, int fnd, ChainArgs& a, const void* V,
                             int* nsums) {
     if (!chain_blk_shape_ok(r2, G, a, fnd) || !padded) return hipErrorInvalidValue;      // (padded blocks: every vector from 4096 rows on)
@@ -86,18 +83,14 @@ hipError_t chain_blk_launch(kh_ctx ctx, int r2, int G, bool onex, bool padded, i
     const int64_t k = a.ncol - 1;
     *nsums = (a.ncol + BLK_BC - 1) / BLK_BC + 1;
     hipError_t e;
-#define KH_BLK(X)                                                 \
-    (fnd == 5 ? launch_blk<4, false, 5, X>(ctx, G, a, bf)         \
-              : (fnd == 7 ? launch_blk<4, false, 7, X>(ctx, G, a, bf) : launch_blk<4, false, 0, X>(ctx, G, a, bf)))
     if (a.debug >= 1 && a.debug <= 3) {        // measurement (kh_bench_kernel 21 .. 23): padded blocks, spread over the chip
         if (onex || !padded || fnd != 0) return hipErrorInvalidValue;
-        e = a.debug == 1 ? launch_blk<4, false, 0, false, 1>(ctx, G, a, bf)
-                         : (a.debug == 2 ? launch_blk<4, false, 0, false, 2>(ctx, G, a, bf)
-                                         : launch_blk<4, false, 0, false, 3>(ctx, G, a, bf));
+        e = dispatch_int<1, 2, 3>(a.debug, [&](auto dbg) { return launch_blk<4, false, 0, false, decltype(dbg)::value>(ctx, G, a, bf); });
     } else {
-        e = onex ? KH_BLK(true) : KH_BLK(false);
+        e = dispatch_bool(onex, [&](auto x) {
+            return dispatch_int<0, 5, 7>(fnd, [&](auto d) { return launch_blk<4, false, decltype(d)::value, decltype(x)::value>(ctx, G, a, bf); });
+        });
     }
-#undef KH_BLK
     if (e == hipSuccess) {
         ctx->blk_V = V;
         ctx->blk_next = k + 1;

@@ -6,6 +6,7 @@
 
 #include "kh_internal.h"
 #include "chain_blk2.h"
+#include "kh_launch.h"
 
 namespace kh {
 
@@ -45,22 +46,17 @@ bool chain_blk2_shape(kh_ctx ctx, int64_t n, int* r2_out, int* g_out, int* cw_ou
 }
 
 template <int R2, bool MASKED, bool XR, bool CW, bool ONE = false>
-static hipError_t launch_blk2(kh_ctx ctx, int G, ChainArgs& a, BlkBufs bf, const XrDev& xr) {
-    static int blocks_per_cu = -1;
-    auto kern = k_mgs_chain_blk2<R2, MASKED, XR, CW, ONE>;
-    if (blocks_per_cu < 0) {
-        int nb = 0;
-        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, CH_BS, 0);
-        if (e != hipSuccess) return e;
-        blocks_per_cu = nb;
-    }
-    if ((int64_t)blocks_per_cu * ctx->ncu < G) return hipErrorCooperativeLaunchTooLarge;      // the sums need every workgroup resident
+static hipError_t launch_blk2(kh_ctx ctx, int G, const ChainArgs& a, BlkBufs bf, const XrDev& xr) {
+    constexpr auto kern = k_mgs_chain_blk2<R2, MASKED, XR, CW, ONE>;
+    int per_cu = 0;
+    const hipError_t e = resident_per_cu<kern>(ctx, CH_BS, 0, &per_cu);
+    if (e != hipSuccess) return e;
+    // workgroups WITHOUT rows in front of the G with rows (chain_blk.h, BlkBufs::nx): when the chip has room for them
     bf.nx = 0;
-    if (ctx->blk_nx > 0 && (int64_t)blocks_per_cu * ctx->ncu >= G + ctx->blk_nx && G + ctx->blk_nx <= CH_GMAX / 2 && G > BLK_PFLAT * (64 / BLK_BC))
+    if (ctx->blk_nx > 0 && (int64_t)per_cu * ctx->ncu >= G + ctx->blk_nx && G + ctx->blk_nx <= CH_GMAX / 2 && G > BLK_PFLAT * (64 / BLK_BC))
         bf.nx = ctx->blk_nx;
     if (bf.nx > 0) ctx->n_blk_rowless += 1;
-    hipLaunchKernelGGL(kern, dim3(G + bf.nx), dim3(CH_BS), 0, ctx->stream, a, bf, xr);
-    return hipGetLastError();
+    return launch_resident<kern>(ctx, G, ResidentShape{CH_BS, G + bf.nx, ctx->ncu, 0}, a, bf, xr);      // the sums need every workgroup resident
 }
 
 // One Arnoldi step k of basis block V (columns 0 .. k, reference order, one sweep; w holds A v_k) on the eight-wave blocked
@@ -110,36 +106,7 @@ int chain_blk2_step(kh_ctx ctx, kh_vec V, const double* w, int64_t wld, int64_t 
         ctx->n_blk_rebuild += 1;
     }
     ChainArgs a;
-    a.xwin = 0;
-    memset(&a, 0, sizeof(a));
-    a.n2 = (n + 1) >> 1;
-    a.chunk2 = chunk2;
-    a.V = V->d;
-    a.B = V->d;
-    a.ld = V->ld;
-    a.col0 = 0;
-    a.ncol = (int)(k + 1);
-    a.sweeps = 1;
-    a.w_in = w;
-    a.vnext = V->col(k + 1);
-    a.hdev = hdev;
-    a.hnext = k + 1;
-    a.gran = ctx->chain_gran;
-    a.xcc_res = ctx->chain_xcc;
-    a.xcc_leader = reinterpret_cast<unsigned*>(ctx->chain_xcc + 128);
-    a.epoch0 = ctx->chain_epoch;
-    a.err = ctx->chain_err;
-    a.debug = ctx->chain_fault ? 4 : 0;
-    a.hpin = hpin;
-    a.hcount = hcount;
-    a.errpin = ctx->chain_err_pin[slot];
-    a.donepin = (hpin != nullptr && ctx->tag_wait) ? ctx->done_pin[slot] : nullptr;
-    if (a.donepin != nullptr) {
-        ctx->done_counter = (ctx->done_counter == 0x7fffffff) ? 1 : ctx->done_counter + 1;
-        a.done_tag = ctx->done_counter;
-        ctx->done_seq[slot] = a.done_tag;
-    }
-    a.n_last = n - 1;
+    chain_args_init(ctx, a, V, w, chunk2, k, hdev, slot, hpin, hcount);
     const int nsums = (a.ncol + BLK_BC - 1) / BLK_BC + 1;
     XrDev xr;
     memset(&xr, 0, sizeof(xr));
@@ -153,24 +120,17 @@ int chain_blk2_step(kh_ctx ctx, kh_vec V, const double* w, int64_t wld, int64_t 
         xr.timeout_ticks = (long long)(ctx->xr_timeout_ms > 0 ? ctx->xr_timeout_ms : 60000) * 100000ll;
     }
     hipError_t e;
-#define KH_B2C(R, C) (multi ? (padded ? launch_blk2<R, false, true, C>(ctx, G, a, bf, xr) : launch_blk2<R, true, true, C>(ctx, G, a, bf, xr)) \
-                            : (padded ? launch_blk2<R, false, false, C>(ctx, G, a, bf, xr) : launch_blk2<R, true, false, C>(ctx, G, a, bf, xr)))
-#define KH_B2(R) (cw ? KH_B2C(R, true) : KH_B2C(R, false))
-#define KH_B2ONE(R) (multi ? (padded ? launch_blk2<R, false, true, true, true>(ctx, G, a, bf, xr) : launch_blk2<R, true, true, true, true>(ctx, G, a, bf, xr)) \
-                           : (padded ? launch_blk2<R, false, false, true, true>(ctx, G, a, bf, xr) : launch_blk2<R, true, false, true, true>(ctx, G, a, bf, xr)))
-    switch (r2) {
-        case 4: e = KH_B2(4); break;
-        case 5: e = KH_B2(5); break;
-        case 6: e = KH_B2(6); break;
-        case 7: e = KH_B2C(7, true); break;
-        case 8: e = KH_B2ONE(8); break;
-        case 9: e = KH_B2ONE(9); break;
-        case 10: e = KH_B2ONE(10); break;
-        default: e = KH_B2ONE(11); break;
-    }
-#undef KH_B2ONE
-#undef KH_B2C
-#undef KH_B2
+    // 4 ... 6 rows per lane: two blocks in registers, with or without the communication wave; 7: with it only; 8 ... 11: ONE block
+    auto launch = [&](auto r, auto c, auto one) {
+        return dispatch_bool(multi, [&](auto x) {
+            return dispatch_bool(!padded, [&](auto m) {
+                return launch_blk2<decltype(r)::value, decltype(m)::value, decltype(x)::value, decltype(c)::value, decltype(one)::value>(ctx, G, a, bf, xr);
+            });
+        });
+    };
+    if (r2 <= 6) e = dispatch_int<4, 5, 6>(r2, [&](auto r) { return dispatch_bool(cw, [&](auto c) { return launch(r, c, std::false_type()); }); });
+    else if (r2 == 7) e = launch(std::integral_constant<int, 7>(), std::true_type(), std::false_type());
+    else e = dispatch_int<8, 9, 10, 11>(r2, [&](auto r) { return launch(r, std::true_type(), std::true_type()); });
     if (e != hipSuccess) {
         (void)hipGetLastError();
         ctx->blk_next = -1;
@@ -180,21 +140,15 @@ int chain_blk2_step(kh_ctx ctx, kh_vec V, const double* w, int64_t wld, int64_t 
         ctx->blk2_refused_n = n;          // (occupancy ...: not tried - nor its table rebuilt - again for vectors of this length)
         return 0;
     }
-    if (a.debug == 4) ctx->chain_fault = 0;
     ctx->blk_V = V;
     ctx->blk_next = k + 1;
     ctx->blk_kind = 2;
-    ctx->chain_epoch += (unsigned)nsums;
     if (multi) {
         ctx->xr_epoch += (unsigned)nsums;
         ctx->n_xr += nsums;
     }
-    ctx->n_chain += 1;
     ctx->n_chain_blk2 += 1;
-    if (hpin == nullptr)
-        KH_HIP(hipMemcpyAsync(ctx->chain_err_pin[slot], ctx->chain_err, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    ctx->wait_tag[slot] = a.donepin != nullptr;
-    return 1;
+    return chain_launched(ctx, slot, a, nsums);
 }
 
 }  // namespace kh

@@ -21,29 +21,16 @@
 
 #include "krylov_steps.h"
 #include "house.h"
+#include "kh_launch.h"
 
 namespace kh {
 
+// the resident launcher (kh_launch.h) on the step's kernel
 template <int R2, bool MASKED, bool CPLX = false>
-static hipError_t launch_house(kh_ctx ctx, int G, HouseArgs& a) {
-    // (cached per process like launch_chain's: one context = one device = one process, single-threaded by the contract
-    // of krylov_hip.h; a second device of another kind in the same process would need the figure per context)
-    static int blocks_per_cu = -1;
+static hipError_t launch_house(kh_ctx ctx, int G, const HouseArgs& a) {
     // (if constexpr: a real launcher must not instantiate the complex kernel of its shape - the 40-row one is not shipped)
-    auto kern = [] {
-        if constexpr (CPLX) return k_zhouse_chain<R2, MASKED>;
-        else return k_house_chain<R2, MASKED>;
-    }();
-    if (blocks_per_cu < 0) {
-        int nb = 0;
-        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, CH_BS, 0);
-        if (e != hipSuccess) return e;
-        blocks_per_cu = nb;
-    }
-    // a plain launch whose grid is checked against the occupancy of the instantiation (krylov_hip.hip: launch_chain)
-    if ((int64_t)blocks_per_cu * ctx->ncu < G) return hipErrorCooperativeLaunchTooLarge;
-    hipLaunchKernelGGL(kern, dim3(G), dim3(CH_BS), 0, ctx->stream, a);
-    return hipGetLastError();
+    if constexpr (CPLX) return launch_resident<k_zhouse_chain<R2, MASKED>>(ctx, G, ResidentShape::chip(ctx, CH_BS, G, 0), a);
+    else return launch_resident<k_house_chain<R2, MASKED>>(ctx, G, ResidentShape::chip(ctx, CH_BS, G, 0), a);
 }
 
 }  // namespace kh
@@ -104,32 +91,16 @@ static int house_begin(kh_ctx ctx, kh_vec Hv, kh_vec Beta, kh_vec V, kh_vec W, i
     a.hpin = ctx->hslot_pin[slot];
     a.errpin = ctx->chain_err_pin[slot];
     a.donepin = ctx->tag_wait ? ctx->done_pin[slot] : nullptr;
-    if (a.donepin != nullptr) {
-        ctx->done_counter = (ctx->done_counter == 0x7fffffff) ? 1 : ctx->done_counter + 1;
-        a.done_tag = ctx->done_counter;
-        ctx->done_seq[slot] = a.done_tag;
-    }
+    if (a.donepin != nullptr) a.done_tag = next_done_tag(ctx, slot);
     hipError_t e;
-#define KH_HOUSE(R, C) (padded ? launch_house<R, false, C>(ctx, G, a) : launch_house<R, true, C>(ctx, G, a))
-    if (cplx) {
-        switch (r2) {        // (40 rows: declined above)
-            case 4: e = KH_HOUSE(4, true); break;
-            case 8: e = KH_HOUSE(8, true); break;
-            case 16: e = KH_HOUSE(16, true); break;
-            case 24: e = KH_HOUSE(24, true); break;
-            default: e = KH_HOUSE(32, true); break;
-        }
-    } else {
-        switch (r2) {
-            case 4: e = KH_HOUSE(4, false); break;
-            case 8: e = KH_HOUSE(8, false); break;
-            case 16: e = KH_HOUSE(16, false); break;
-            case 24: e = KH_HOUSE(24, false); break;
-            case 32: e = KH_HOUSE(32, false); break;
-            default: e = KH_HOUSE(40, false); break;
-        }
-    }
-#undef KH_HOUSE
+    if (cplx)        // (40 rows: declined above)
+        e = dispatch_int<4, 8, 16, 24, 32>(r2, [&](auto r) {
+            return padded ? launch_house<decltype(r)::value, false, true>(ctx, G, a) : launch_house<decltype(r)::value, true, true>(ctx, G, a);
+        });
+    else
+        e = dispatch_int<4, 8, 16, 24, 32, 40>(r2, [&](auto r) {
+            return padded ? launch_house<decltype(r)::value, false>(ctx, G, a) : launch_house<decltype(r)::value, true>(ctx, G, a);
+        });
     if (e != hipSuccess) {
         // e.g. hipErrorCooperativeLaunchTooLarge: not all workgroups can be co-resident.  A property of this shape on this
         // device: vectors of this length take the per-reflector path from now on

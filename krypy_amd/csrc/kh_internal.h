@@ -85,6 +85,9 @@ struct kh_ctx_s {
     int chain_in_recovery = 0;       // kh_arnoldi_step_end is re-running a step: no re-arming from inside it
     int64_t n_chain_rearmed = 0;     // times the chain family was switched on again (kh_ctx_get "n_chain_rearmed")
     int64_t chain_refused_n = -1;    // vector length whose chain launch the runtime refused (occupancy): that shape only
+    int chain_lds_failed = 0;        // the LDS-parking / PF kernel could not be launched once: the plain kernel from then on ...
+    int chain_long_failed = 0;       // ... and the 48-row long kernel: k_mgs_chain<48>.  kh_ctx_set "chain" forgets all three; setting
+                                     // "chain_lds" / "chain_long" back to 1 does NOT (as it never did for the refused length)
     // Householder Arnoldi in one launch (house.h; kh_ctx_set "house_chain"): its own switch and timeout count - a timed-out
     // launch is re-run by the host layer on the per-reflector path and the next step tries the kernel again; the third
     // timeout in one context leaves it off
@@ -246,6 +249,8 @@ struct kh_ctx_s {
     int64_t n_xr_fused = 0;                            // ... of which in the same launch as the reduction of the partial sums
 };
 
+// (tests/support/chain_dispatch_cases.py mirrors the first four fields - ctx, n, ncols, ld - to shorten ld of a block by hand:
+// keep _VecHead there in step with this layout)
 struct kh_vec_s {
     kh_ctx ctx;
     int64_t n, ncols, ld;
@@ -331,6 +336,12 @@ struct kh_proj_s {
 };
 
 namespace kh {
+// the completion tag of the launch that will finish the step parked in `slot` (kh_ctx_s::done_pin): drawn, and remembered for the wait
+static inline int next_done_tag(kh_ctx ctx, int slot) {
+    ctx->done_counter = (ctx->done_counter == 0x7fffffff) ? 1 : ctx->done_counter + 1;
+    ctx->done_seq[slot] = ctx->done_counter;
+    return ctx->done_counter;
+}
 // comm.hip
 int comm_allreduce_dev(kh_ctx ctx, double* dev, int64_t count);
 int comm_halo_exchange(kh_ctx ctx, kh_mat A, const double* x, hipStream_t stream, int width = 1);
@@ -346,7 +357,7 @@ int reduce_partials_allreduce(kh_ctx ctx, const double* part, int nb, int pstrid
 void xr_free(kh_ctx ctx);
 void xh_free(kh_mat A);
 int xr_check(kh_ctx ctx);           // KH_ERR_COMM when an exchange has timed out since the last look
-// krylov_hip.hip
+// krylov_hip.hip: the banded copy of a sharded operator rebuilt with its ghost columns
 int dia_rebuild_for_halo(kh_ctx ctx, kh_mat A);
 // chain_blk.hip
 struct ChainArgs;
@@ -373,8 +384,15 @@ int chain_blk2_step(kh_ctx ctx, kh_vec V, const double* w, int64_t wld, int64_t 
 // chain_xr.hip: the register-resident chain kernels (16 ... 56 rows per lane) with the cross-rank stage in every sum
 bool chain_xr_shape(kh_ctx ctx, int64_t n, int* r2_out, int* g_out);
 int chain_xr_step(kh_ctx ctx, kh_vec V, const double* w, int64_t wld, int64_t k, double* hdev, int slot, double* hpin, int hcount);
-// krylov_hip.hip: the epoch counter of the grid-wide sums brought back to 1 when it nears its wrap; <V[:, j0 .. j0+ncols), w> on the device
+// chain_launch.hip: the epoch counter of the grid-wide sums brought back to 1 when it nears its wrap; the argument block of a
+// reference-order step on columns 0 .. k of V (zeroed, the fields every chain family fills alike, the completion tag drawn) and
+// what every successful launch leaves behind (fake timeout cleared, n_chain, nsums epochs, the error word's copy when there is
+// no pinned H slot, wait_tag[slot]; returns 1)
 int chain_epoch_check(kh_ctx ctx);
+void chain_args_init(kh_ctx ctx, ChainArgs& a, kh_vec V, const double* w, int64_t chunk2, int64_t k, double* hdev, int slot, double* hpin,
+                     int hcount);
+int chain_launched(kh_ctx ctx, int slot, const ChainArgs& a, int nsums);
+// krylov_hip.hip: <V[:, j0 .. j0+ncols), w> on the device
 int dot_panel_raw(kh_ctx ctx, kh_vec V, int64_t j0, int64_t ncols, const double* w, double* out_dev);
 void chain_blk_free(kh_ctx ctx);
 // proj_reg.hip

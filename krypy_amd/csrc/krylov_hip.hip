@@ -11,9 +11,9 @@
 
 #include "kernels.h"
 #include "chain.h"
-#include "chain_long.h"
 #include "lanczos.h"
 #include "krylov_steps.h"
+#include "kh_launch.h"
 #include <stdlib.h>
 
 extern "C" {
@@ -302,15 +302,6 @@ static void launch_dia_nd(kh_ctx ctx, kh_mat A, const DiaOffs& o, const double* 
                        aux, A->part, rg.blk_lo, rg.blk_skip, rg.part_off, XhArgs());
 }
 
-// the offsets of a banded operator, and - mask form - the values of its diagonals
-static DiaOffs dia_offs(const kh_mat_s* A) {
-    DiaOffs o;
-    o.nd = A->dia_nd;
-    for (int d = 0; d < KH_DIA_MAX; ++d) o.off[d] = d < A->dia_nd ? A->dia_off[d] : 0;
-    for (int d = 0; d < KH_DIA_CMAX; ++d) o.cst[d] = (A->dmask != nullptr && d < A->dia_nd) ? A->dia_cst[d] : 0.0;
-    return o;
-}
-
 template <int EPI>
 static void launch_dia(kh_ctx ctx, kh_mat A, const double* x, double* y, const double* aux, const SpmvRange& rg) {
     const DiaOffs o = dia_offs(A);
@@ -445,661 +436,8 @@ int apply_one(kh_ctx ctx, kh_mat A, const double* x, double* y, int epi, const d
     return 0;
 }
 
-// ---- register-resident MGS chain (chain.h) -------------------------------------------------
-// Plain launch (a cooperative launch goes through a separate hardware queue and costs ~1 ms of
-// cross-queue synchronisation per Arnoldi step when interleaved with ordinary kernels).  Residency
-// is what matters for the in-kernel grid reduction, and it is identical for plain and cooperative
-// launches: it is checked here against the occupancy of this instantiation, and every spin in the
-// kernel is bounded.
-template <int R2, bool MASKED, bool CPLX = false, int FND = 0, int WL = 0>
-static hipError_t launch_chain(kh_ctx ctx, int G, ChainArgs& a) {
-    static int blocks_per_cu = -1;
-    constexpr size_t lds = (size_t)WL * CH_BS * sizeof(double2);      // rows of w that live in LDS (long vectors)
-    if (blocks_per_cu < 0) {
-        if (lds > 0) {
-            hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mgs_chain<R2, MASKED, CPLX, FND, WL>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e0 != hipSuccess) return e0;
-        }
-        int nb = 0;
-        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_mgs_chain<R2, MASKED, CPLX, FND, WL>, CH_BS, lds);
-        if (e != hipSuccess) return e;
-        blocks_per_cu = nb;
-    }
-    if ((int64_t)blocks_per_cu * ctx->ncu < G) return hipErrorCooperativeLaunchTooLarge;
-    hipLaunchKernelGGL((k_mgs_chain<R2, MASKED, CPLX, FND, WL>), dim3(G), dim3(CH_BS), lds, ctx->stream, a);
-    return hipGetLastError();
-}
-
-// the variant that parks the head of every column in LDS between its dot and its update (B == V)
-template <int R2, bool MASKED, bool CPLX = false, int FND = 0>
-static hipError_t launch_chain_lds(kh_ctx ctx, int G, ChainArgs& a) {
-    static int blocks_per_cu = -1;
-    constexpr size_t lds = ChainShapeLds<R2, CPLX>::LDS_BYTES;
-    if (blocks_per_cu < 0) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mgs_chain_lds<R2, MASKED, CPLX, FND>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        int nb = 0;
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_mgs_chain_lds<R2, MASKED, CPLX, FND>, CH_BS, lds);
-        if (e != hipSuccess) return e;
-        blocks_per_cu = nb;
-    }
-    if ((int64_t)blocks_per_cu * ctx->ncu < G) return hipErrorCooperativeLaunchTooLarge;
-    hipLaunchKernelGGL((k_mgs_chain_lds<R2, MASKED, CPLX, FND>), dim3(G), dim3(CH_BS), lds, ctx->stream, a);
-    return hipGetLastError();
-}
-
-// 48 rows per lane with a third of every column kept on the chip between its two uses (chain_long.h)
-template <int FND>
-static hipError_t launch_chain_long(kh_ctx ctx, int G, ChainArgs& a) {
-    static int blocks_per_cu = -1;
-    constexpr size_t lds = ChainShapeLong::LDS_BYTES;
-    if (blocks_per_cu < 0) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mgs_chain_long<FND, false>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        int nb = 0;
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_mgs_chain_long<FND, false>, CH_BS, lds);
-        if (e != hipSuccess) return e;
-        blocks_per_cu = nb;
-    }
-    if ((int64_t)blocks_per_cu * ctx->ncu < G) return hipErrorCooperativeLaunchTooLarge;
-    hipLaunchKernelGGL((k_mgs_chain_long<FND, false>), dim3(G), dim3(CH_BS), lds, ctx->stream, a);
-    return hipGetLastError();
-}
-
-// the variant that keeps HBM busy through the update phase (chain.h: k_mgs_chain_pf)
-template <int R2, bool MASKED, bool CPLX = false, int FND = 0>
-static hipError_t launch_chain_pf(kh_ctx ctx, int G, ChainArgs& a) {
-    static int blocks_per_cu = -1;
-    constexpr size_t lds = ChainShapePf<R2>::LDS_BYTES;
-    if (blocks_per_cu < 0) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mgs_chain_pf<R2, MASKED, CPLX, FND>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        int nb = 0;
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_mgs_chain_pf<R2, MASKED, CPLX, FND>, CH_BS, lds);
-        if (e != hipSuccess) return e;
-        blocks_per_cu = nb;
-    }
-    if ((int64_t)blocks_per_cu * ctx->ncu < G) return hipErrorCooperativeLaunchTooLarge;
-    hipLaunchKernelGGL((k_mgs_chain_pf<R2, MASKED, CPLX, FND>), dim3(G), dim3(CH_BS), lds, ctx->stream, a);
-    return hipGetLastError();
-}
-
-// short vectors: all working workgroups on one XCD (chain.h, ONEX).  8 G + 8 workgroups are launched; the G that
-// work must be co-resident on the 1/8 of the CUs one XCD has.
-template <int R2, bool MASKED, bool CPLX, bool PF>
-static hipError_t launch_chain_onex(kh_ctx ctx, int G, ChainArgs& a) {
-    static int blocks_per_cu = -1;
-    constexpr size_t lds = PF ? ChainShapePf<R2>::LDS_BYTES : 0;
-    auto kern = PF ? k_mgs_chain_pf<R2, MASKED, CPLX, 0, true> : k_mgs_chain<R2, MASKED, CPLX, 0, 0, true>;
-    if (blocks_per_cu < 0) {
-        if (lds > 0) {
-            hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e0 != hipSuccess) return e0;
-        }
-        int nb = 0;
-        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, CH_BS, lds);
-        if (e != hipSuccess) return e;
-        blocks_per_cu = nb;
-    }
-    if ((int64_t)blocks_per_cu * (ctx->ncu / 8) < G) return hipErrorCooperativeLaunchTooLarge;
-    hipLaunchKernelGGL(kern, dim3(8 * G + 8), dim3(CH_BS), lds, ctx->stream, a);
-    return hipGetLastError();
-}
-
-// short vectors without a preconditioner: whole columns in a register ring, requested several links ahead
-// (chain.h, k_mgs_chain_small); ONEX or spread over the chip
-template <int R2, bool MASKED, int FND, bool ONEX, bool DMASK = false>
-static hipError_t launch_chain_small(kh_ctx ctx, int G, ChainArgs& a) {
-    static int blocks_per_cu = -1;
-#ifndef KH_SMALL_LA4
-#define KH_SMALL_LA4 3
-#define KH_SMALL_LA8 2
-#endif
-    constexpr int LA = (R2 == 4) ? KH_SMALL_LA4 : KH_SMALL_LA8;          // columns requested ahead
-    auto kern = k_mgs_chain_small<R2, LA, MASKED, FND, ONEX, DMASK>;
-    if (blocks_per_cu < 0) {
-        int nb = 0;
-        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, ONEX ? CH_BS + 64 : CH_BS, 0);
-        if (e != hipSuccess) return e;
-        blocks_per_cu = nb;
-    }
-    if ((int64_t)blocks_per_cu * (ONEX ? ctx->ncu / 8 : ctx->ncu) < G) return hipErrorCooperativeLaunchTooLarge;
-    hipLaunchKernelGGL(kern, dim3(ONEX ? 8 * G + 8 : G), dim3(ONEX ? CH_BS + 64 : CH_BS), 0, ctx->stream, a);   // ONEX: + the communication wave
-    return hipGetLastError();
-}
-
-// ... with the banded operator in the prologue (no SpMV launch in front of the step)
-template <int R2, int FND, bool PF>
-static hipError_t launch_chain_onex_fused(kh_ctx ctx, int G, ChainArgs& a) {
-    static int blocks_per_cu = -1;
-    constexpr size_t lds = PF ? ChainShapePf<R2>::LDS_BYTES : 0;
-    auto kern = PF ? k_mgs_chain_pf<R2, false, false, FND, true> : k_mgs_chain<R2, false, false, FND, 0, true>;
-    if (blocks_per_cu < 0) {
-        if (lds > 0) {
-            hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e0 != hipSuccess) return e0;
-        }
-        int nb = 0;
-        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, CH_BS, lds);
-        if (e != hipSuccess) return e;
-        blocks_per_cu = nb;
-    }
-    if ((int64_t)blocks_per_cu * (ctx->ncu / 8) < G) return hipErrorCooperativeLaunchTooLarge;
-    hipLaunchKernelGGL(kern, dim3(8 * G + 8), dim3(CH_BS), lds, ctx->stream, a);
-    return hipGetLastError();
-}
-
-// one Lanczos step in three passes (lanczos.h)
-template <int R2, int FND, bool JAC, bool MR>
-static hipError_t launch_lanczos(kh_ctx ctx, int G, ChainArgs& a, const MinresJob& mr) {
-    static int blocks_per_cu = -1;
-    constexpr size_t lds = (size_t)(LanczosShape<R2>::WL + (JAC ? LanczosShape<R2>::DL : 0)) * CH_BS * sizeof(double2);
-    if (blocks_per_cu < 0) {
-        if (lds > 0) {
-            hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lanczos_fused<R2, FND, JAC, MR>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e0 != hipSuccess) return e0;
-        }
-        int nb = 0;
-        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_lanczos_fused<R2, FND, JAC, MR>, CH_BS, lds);
-        if (e != hipSuccess) return e;
-        blocks_per_cu = nb;
-    }
-    if ((int64_t)blocks_per_cu * ctx->ncu < G) return hipErrorCooperativeLaunchTooLarge;
-    hipLaunchKernelGGL((k_lanczos_fused<R2, FND, JAC, MR>), dim3(G), dim3(CH_BS), lds, ctx->stream, a, mr);
-    return hipGetLastError();
-}
-
-// rows-per-workgroup (= template R2) and grid of the chain kernel for vectors of length n
-bool chain_geometry(kh_ctx ctx, int64_t n, int* r2_out, int* g_out, bool onex) {
-    if (n < 2) return false;
-    // an odd n is handled as n+1: the extra element is the (always zero) padding behind the column
-    const int64_t n2 = (n + 1) >> 1;
-    static const int kR2[] = {4, 8, 16, 24, 32, 40, 48, 56};   // 48 / 56: the last 8 / 16 rows of w live in LDS
-    // short vectors: as few workgroups as one XCD has CUs, so that all of them can run there (chain.h, ONEX) - 8 rows
-    // per lane on 32 workgroups beat 4 rows on 64 spread over the chip, the sum being the whole link
-    if (onex) {
-        if (!ctx->chain_onex || ctx->ncu % 8 != 0) return false;
-        for (int c : {4, 8}) {
-            const int64_t g = (n2 + (int64_t)c * CH_BS - 1) / ((int64_t)c * CH_BS);
-            if (g <= ctx->ncu / 8 && g <= 32) {
-                *r2_out = c;
-                *g_out = (int)g;
-                return true;
-            }
-        }
-        return false;
-    }
-    for (int c : kR2) {
-        const int64_t g = (n2 + (int64_t)c * CH_BS - 1) / ((int64_t)c * CH_BS);
-        if (g <= ctx->ncu && g <= CH_GMAX) {
-            *r2_out = c;
-            *g_out = (int)g;
-            return true;
-        }
-    }
-    return false;   // w fits neither registers nor registers + LDS (N > 14.68 M on 256 CUs): stream it (k_gs_link)
-}
-
-// leading dimension of a block of n-vectors: large vectors are padded to whole chain chunks so
-// that the predicate-free kernel applies (<= 0.4 % extra memory at N = 10^7)
-static int64_t padded_ld(kh_ctx ctx, int64_t n) {
-    int64_t ld = ((n + 31) / 32) * 32;
-    int r2 = 0, g = 0;
-    // (from 4096 rows on: below that a vector is a fraction of one workgroup's chunk)
-    if (n >= (1 << 12) && chain_geometry(ctx, n, &r2, &g)) ld = (int64_t)g * r2 * CH_BS * 2;
-    if (n >= (1 << 12) && chain_geometry(ctx, n, &r2, &g, true)) ld = std::max(ld, (int64_t)g * r2 * CH_BS * 2);   // (one-XCD shape)
-    int cw = 0;
-    if (n >= (1 << 12) && chain_blk2_shape(ctx, n, &r2, &g, &cw, ctx->blk2_one >= 1))      // (chain_blk2.h: 4 ... 11 rows, 448 or 512 lanes with rows)
-        ld = std::max(ld, (int64_t)g * r2 * (cw ? CH_BS - 64 : CH_BS) * 2);
-    return ld == 0 ? 32 : ld;
-}
-
-#define KH_BLK_MIN_LINKS 8     // Gram-Schmidt links from which the blocked kernel (chain_blk.h) takes a step of short vectors
-// true when the step goes to the blocked kernel (which has no operator prologue yet)
-static inline bool blk_takes_step(kh_ctx ctx, const ChainArgs& a, int r2) {
-    return ctx->chain_blk && r2 == 4 && !a.presub && a.sweeps == 1 && a.col0 == 0 && a.ncol >= KH_BLK_MIN_LINKS &&
-           a.ncol + 2 <= KH_BLK_TABCOLS && !kh_multi(ctx);
-}
-
-// returns 1 if the chain was launched, 0 if this step is not eligible (caller uses the link
-// kernels), negative on error
-// the epoch counter of the grid-wide sums nears its wrap: everything that carries tags is zeroed, the count starts over
-int chain_epoch_check(kh_ctx ctx) {
-    if (ctx->chain_epoch <= 0xfff00000u) return 0;
-    KH_HIP(hipStreamSynchronize(ctx->stream));
-    KH_HIP(hipMemset(ctx->chain_gran, 0, sizeof(unsigned long long) * 4 * CH_GMAX));
-    KH_HIP(hipMemset(ctx->chain_xcc, 0, sizeof(unsigned long long) * 128 + sizeof(unsigned) * 16));
-    if (ctx->blk_gran != nullptr) {
-        // (the blocked kernels' granules only: chain_blk_reset leaves the Gram table of the running Arnoldi sequence
-        // alone when the buffer exists - ADVICE r04: a zeroed table behind a still matching (blk_V, blk_next) key
-        // silently dropped the corrections.  The key is withdrawn as well: the next blocked step rebuilds its rows.)
-        KH_HIP(chain_blk_reset(ctx));
-        KH_HIP(hipStreamSynchronize(ctx->stream));
-        ctx->blk_next = -1;
-    }
-    ctx->chain_epoch = 1;
-    ctx->n_epoch_wraps += 1;
-    return 0;
-}
-
 int dot_panel_raw(kh_ctx ctx, kh_vec V, int64_t j0, int64_t ncols, const double* w, double* out_dev) {
     return ::dot_panel_dev(ctx, V, j0, ncols, w, out_dev, 0);
-}
-
-int try_chain(kh_ctx ctx, kh_vec V, kh_vec B, const double* w, int64_t wld, const double* dg,
-              kh_vec P, int64_t k, int64_t start, int sweeps, bool presub, double h_km1,
-              const double* h_km1_dev, double* hdev, int slot, bool cplx, double* hpin,
-              int hcount, kh_mat Afuse, const double* xk, const MinresJob* mr) {
-    // Afuse: compute w = Afuse * xk in the kernel's prologue instead of reading w (banded operators;
-    // returns 0 without launching anything when that variant does not apply - the caller then runs the
-    // SpMV and calls again without Afuse)
-    // cplx: V, B, w are (re, im) views of complex vectors (zpath.h); hdev holds (re, im) pairs
-    if (!ctx->chain_enabled || kh_multi(ctx)) return 0;
-    if (cplx && (dg != nullptr || P != nullptr)) return 0;
-    const int64_t n = V->n;
-    if (n == ctx->chain_refused_n) return 0;
-    const int64_t n2 = (n + 1) >> 1;
-    int r2 = 0, G = 0;
-    if (!chain_geometry(ctx, n, &r2, &G)) return 0;
-    // short vectors with at least a few links in the launch: as few workgroups as one XCD has CUs, all of them
-    // there (chain.h, ONEX) - the sum is the whole link.  (One or two links - Lanczos, the first Arnoldi steps - do
-    // not pay for the larger grid: MINRES + Jacobi at N = 10^5 32,400 vs 27,400 it/s.)
-    bool want_onex = false;
-    if ((k - start + 1) * sweeps >= 3 && (ctx->chain_debug == 0) && ctx->onex_ticket != nullptr) {
-        int r2x = 0, Gx = 0;
-        // (the column-ring kernel with 8 rows per lane - 1.3e5 < N <= 2.6e5 - is faster spread over the chip with 4:
-        // a one-XCD link moves the whole column through one XCD's port; 7,240 vs 6,770 it/s at N = 2.5e5)
-        const bool ring_kernel = ctx->chain_small && B == V && dg == nullptr && !cplx;
-        // (... and the blocked kernel - four times fewer sums - is bound by the one XCD's memory port from
-        // ctx->blk_onex_maxn rows on: it then spreads over the chip as well)
-        const bool blk_long = ctx->chain_blk && ring_kernel && !presub && sweeps == 1 && start == 0 &&
-                              k + 1 >= KH_BLK_MIN_LINKS && r2 == 4 && n > ctx->blk_onex_maxn;
-        if (chain_geometry(ctx, n, &r2x, &Gx, true) && !(ring_kernel && r2x == 8 && r2 == 4) && !blk_long) {
-            r2 = r2x;
-            G = Gx;
-            want_onex = true;
-        }
-    }
-    if (cplx && 4 * G > 2 * CH_GMAX) return 0;      // grid_sum2: four granules per workgroup
-    if ((n & 1) && (V->ld <= n || B->ld <= n || wld <= n || (P && P->ld <= n))) return 0;
-    // 1.05 M ... 2.5 M rows (8 / 16 rows per lane in the general geometry, 5 ... 11 here), no preconditioner, a long chain: the
-    // eight-wave blocked kernel (chain_blk2.h) - one grid-wide sum per four columns, columns read once.  It loads w: with the
-    // operator to be fused (Afuse) nothing is launched here, the caller runs the SpMV and comes back without it.
-    {
-        int r2b = 0, Gb = 0;
-        if (ctx->chain_blk2 && ctx->chain_blk && ctx->chain_small && (r2 == 8 || (r2 == 16 && ctx->blk2_one >= 2)) && !want_onex && B == V && dg == nullptr && !cplx && !presub &&
-            sweeps == 1 && start == 0 && k + 1 >= KH_BLK_MIN_LINKS && (ctx->chain_debug == 0) && n != ctx->blk2_refused_n &&
-            chain_blk2_shape(ctx, n, &r2b, &Gb, nullptr, ctx->blk2_one >= 2) && r2b > 4) {
-            if (Afuse != nullptr) return 0;
-            const int rc = chain_blk2_step(ctx, V, w, wld, k, hdev, slot, hpin, hcount, false);
-            if (rc != 0) {
-                if (rc == 1) ctx->n_chain_lds += 1;      // (the column is used twice from the chip: counted with that family)
-                return rc;
-            }
-        }
-    }
-    const int64_t chunk2 = (int64_t)r2 * CH_BS;
-    // predicate-free kernel iff every block involved is padded to G whole chunks
-    const int64_t need_ld = (int64_t)G * chunk2 * 2;
-    const bool padded = V->ld >= need_ld && B->ld >= need_ld && (P == nullptr || P->ld >= need_ld) &&
-                        wld >= need_ld;
-    KH_TRY(chain_epoch_check(ctx));
-    ChainArgs a;
-    a.xwin = 0;
-    a.n2 = n2;
-    a.chunk2 = chunk2;
-    a.V = V->d;
-    a.B = B->d;
-    a.ld = V->ld;
-    a.col0 = start;
-    a.ncol = (int)(k - start + 1);
-    a.sweeps = sweeps;
-    a.w_in = w;
-    a.dg = dg;
-    a.vnext = V->col(k + 1);
-    a.pnext = P ? P->col(k + 1) : nullptr;
-    a.hdev = hdev;
-    a.hnext = cplx ? 2 * (k + 1) : k + 1;
-    a.gran = ctx->chain_gran;
-    a.xcc_res = ctx->chain_xcc;
-    a.xcc_leader = reinterpret_cast<unsigned*>(ctx->chain_xcc + 128);
-    a.epoch0 = ctx->chain_epoch;
-    a.err = ctx->chain_err;
-    a.debug = ctx->chain_debug;
-    if (ctx->chain_fault) a.debug = 4;     // kh_ctx_set("chain_fault", 1): the next launch behaves like a timed-out one
-    a.presub = presub ? 1 : 0;
-    a.h_km1 = h_km1;
-    a.h_km1_dev = h_km1_dev;
-    a.bprev = presub ? B->col(k - 1) : nullptr;
-    a.hpin = hpin;
-    a.hcount = hcount;
-    a.errpin = ctx->chain_err_pin[slot];
-    // completion tag (kh_internal.h): whichever chain-family kernel this call ends up launching writes it
-    a.donepin = (hpin != nullptr && ctx->tag_wait) ? ctx->done_pin[slot] : nullptr;
-    a.done_tag = 0;
-    if (a.donepin != nullptr) {
-        ctx->done_counter = (ctx->done_counter == 0x7fffffff) ? 1 : ctx->done_counter + 1;
-        a.done_tag = ctx->done_counter;
-        ctx->done_seq[slot] = a.done_tag;
-    }
-#ifdef KH_CHAIN_TRACE
-    a.trace = ctx->chain_trace;
-#endif
-    hipError_t e;
-    const int lds_env = ctx->chain_lds;
-    // (the complex instantiation with 40 rows per lane spills 36 registers with the LDS traffic on top
-    // and still beats the plain kernel, 769 vs 677 it/s at N = 5*10^6; 32 rows fit without spills since
-    // both parts of the coefficient share one grid reduction)
-    static thread_local bool lds_failed = false;   // the LDS variant could not be launched once: plain kernel from then on
-    // (an unpadded block of a long vector - not what kh_vec_alloc produces - takes the plain kernel: the
-    // masked LDS instantiations with 32 / 40 rows spill)
-    bool use_lds = lds_env && !lds_failed && B == V && dg == nullptr && (a.debug == 0 || a.debug == 4) &&
-                   (padded || r2 <= 24) && r2 <= 40;     // (48 / 56 rows: LDS holds a part of w itself)
-    if (r2 > 40 && cplx) return 0;
-    // 48 rows per lane, no preconditioner, padded blocks: a third of every column stays on the chip between its two uses
-    static thread_local bool long_failed = false;
-    bool use_long = ctx->chain_long && ctx->chain_lds && !long_failed && r2 == 48 && B == V && dg == nullptr && !cplx && padded && (a.debug == 0 || a.debug == 4);
-    // fused operator: the padded real kernels with 16 ... 40 rows per lane (N > 2.1 M) have that prologue
-    bool fused = false;
-    if (Afuse != nullptr) {
-        // (a step with one Gram-Schmidt link has the three-pass kernel of lanczos.h for every shape up to 40 rows)
-        const bool lz_shape = ctx->lanczos_fused && a.ncol == 1 && a.sweeps == 1 && (dg == nullptr || P != nullptr) &&
-                              (r2 == 4 || r2 == 8);
-        const bool small_shape = ctx->chain_small && r2 <= 8 && B == V && dg == nullptr;
-        if (cplx) {
-            // complex banded operator (zpath.h: zdia, leading dimension and rows counted in complex entries): the padded
-            // chain kernels with 16 ... 40 rows per lane, spread over the chip
-            fused = ctx->chain_spmv && padded && ((a.debug & 3) == 0) && r2 >= 16 && r2 <= 40 && !want_onex && xk != nullptr &&
-                    Afuse->kind == KH_MAT_ZCSR && Afuse->zdia != nullptr && (Afuse->dia_nd == 5 || Afuse->dia_nd == 7) &&
-                    2 * Afuse->n_rows == n && Afuse->nrecv_prev + Afuse->nrecv_next == 0 && 2 * Afuse->zdia_ld >= need_ld;
-        } else {
-            fused = ctx->chain_spmv && padded && ((a.debug & 3) == 0) && ((r2 >= 16 && r2 <= 48) || want_onex || lz_shape || small_shape) && xk != nullptr &&
-                    Afuse->kind == KH_MAT_CSR && kh_banded(Afuse) && (Afuse->dia_nd == 5 || Afuse->dia_nd == 7) &&
-                    Afuse->n_rows == n && Afuse->nrecv_prev + Afuse->nrecv_next == 0 && Afuse->dia_ld >= need_ld;
-        }
-        if (!fused) return 0;
-        a.dia = cplx ? Afuse->zdia : Afuse->dia;
-        a.dmask = cplx ? nullptr : Afuse->dmask;
-        a.dia_ld = cplx ? Afuse->zdia_ld : Afuse->dia_ld;
-        a.xk = xk;
-        a.n_last = cplx ? Afuse->n_rows - 1 : n - 1;
-        a.offs = dia_offs(Afuse);
-    } else {
-        a.dia = nullptr;
-        a.dmask = nullptr;
-        a.dia_ld = 0;
-        a.xk = nullptr;
-        a.n_last = n - 1;
-        a.offs.nd = 0;
-    }
-#define KH_CHAIN_PLAIN(R)                                                                             \
-    (cplx ? (padded ? launch_chain<R, false, true>(ctx, G, a) : launch_chain<R, true, true>(ctx, G, a)) \
-          : (padded ? launch_chain<R, false>(ctx, G, a) : launch_chain<R, true>(ctx, G, a)))
-#define KH_CHAIN_LDS(R)                                                                                       \
-    (cplx ? (padded ? launch_chain_lds<R, false, true>(ctx, G, a) : launch_chain_lds<R, true, true>(ctx, G, a)) \
-          : (padded ? launch_chain_lds<R, false>(ctx, G, a) : launch_chain_lds<R, true>(ctx, G, a)))
-#define KH_CHAIN_PF(R)                                                                                      \
-    (cplx ? (padded ? launch_chain_pf<R, false, true>(ctx, G, a) : launch_chain_pf<R, true, true>(ctx, G, a)) \
-          : (padded ? launch_chain_pf<R, false>(ctx, G, a) : launch_chain_pf<R, true>(ctx, G, a)))
-    // k_mgs_chain_pf wins where the whole column stays on chip (<= 24 rows per lane: 6.9 vs 7.2 us per link at
-    // N = 4*10^6); with 32 / 40 rows its prefetches sit in the CU's memory queue in front of the reduction's polls
-    // and cost what they save (17.4 vs 16.3 us per link at N = 10^7)
-    const bool use_pf = use_lds && ctx->chain_pf && (r2 <= 24 || (ctx->chain_pf == 2 && r2 <= 40));   // (2: measurement)
-#define KH_CHAIN(R) (use_lds ? (use_pf ? KH_CHAIN_PF(R) : KH_CHAIN_LDS(R)) : KH_CHAIN_PLAIN(R))
-    // a step with ONE Gram-Schmidt link (Lanczos / MINRES, the first Arnoldi step): three passes instead of six
-    if (fused && !cplx && r2 <= 40 && ctx->lanczos_fused && a.ncol == 1 && a.sweeps == 1 && (dg == nullptr || P != nullptr)) {
-        if (!presub) {                 // no previous column: subtract 0 * (some valid column)
-            a.bprev = B->col(k);
-            a.h_km1 = 0.0;
-            a.h_km1_dev = nullptr;
-        }
-        MinresJob job;
-        if (mr != nullptr) job = *mr;
-        else {
-            job.on = 0;
-            job.v = job.w1 = w;           // (never dereferenced)
-            job.w0 = job.yk = const_cast<double*>(w);
-            job.r0 = job.r1 = job.y0 = 0.0;
-            job.r2 = 1.0;
-        }
-#define KH_LZ(R, D)                                                                                             \
-    (dg != nullptr ? (job.on ? launch_lanczos<R, D, true, true>(ctx, G, a, job) : launch_lanczos<R, D, true, false>(ctx, G, a, job)) \
-                   : (job.on ? launch_lanczos<R, D, false, true>(ctx, G, a, job) : launch_lanczos<R, D, false, false>(ctx, G, a, job)))
-        if (r2 == 40) e = (a.offs.nd == 5) ? KH_LZ(40, 5) : KH_LZ(40, 7);
-        else if (r2 == 32) e = (a.offs.nd == 5) ? KH_LZ(32, 5) : KH_LZ(32, 7);
-        else if (r2 == 24) e = (a.offs.nd == 5) ? KH_LZ(24, 5) : KH_LZ(24, 7);
-        else if (r2 == 16) e = (a.offs.nd == 5) ? KH_LZ(16, 5) : KH_LZ(16, 7);
-        else if (r2 == 8) e = (a.offs.nd == 5) ? KH_LZ(8, 5) : KH_LZ(8, 7);
-        else e = (a.offs.nd == 5) ? KH_LZ(4, 5) : KH_LZ(4, 7);
-#undef KH_LZ
-        if (e == hipSuccess) {
-            if (a.debug == 4) ctx->chain_fault = 0;
-            ctx->n_chain += 1;
-            ctx->n_chain_fused += 1;
-            ctx->n_dia_mask += a.dmask != nullptr ? 1 : 0;
-            ctx->n_lanczos_fused += 1;
-            ctx->chain_epoch += 2u;          // the coefficient's and the norm's grid-wide sums
-            if (hpin == nullptr)
-                KH_HIP(hipMemcpyAsync(ctx->chain_err_pin[slot], ctx->chain_err, sizeof(int), hipMemcpyDeviceToHost,
-                                      ctx->stream));
-            ctx->mr_taken = job.on ? 1 : 0;     // (the MINRES job - if any - went along)
-            { ctx->wait_tag[slot] = a.donepin != nullptr; return 1; }
-        }
-        (void)hipGetLastError();             // e.g. the dynamic LDS was refused: the general chain kernel below
-        if (!presub) a.bprev = nullptr;
-    }
-    // short vectors (4 ... 32 workgroups of 4 / 8 rows per lane): a link is its grid-wide sum - all working
-    // workgroups on ONE XCD, where the sum is an L2 round trip (chain.h, ONEX)
-    // short vectors, no preconditioner, real data: the column-ring kernel (one read per column, several links of look-ahead)
-    const bool blk_debug = (a.debug >= 1 && a.debug <= 3) && !fused && padded && blk_takes_step(ctx, a, r2);   // measurement modes of the blocked kernel
-    if (ctx->chain_small && r2 <= 8 && B == V && dg == nullptr && !cplx && (a.debug == 0 || a.debug == 4 || blk_debug) &&
-        !(fused && ctx->lanczos_fused && a.ncol == 1 && a.sweeps == 1)) {
-        if (want_onex) {
-            const unsigned slot_ = (unsigned)(ctx->n_chain_onex & 255);
-            a.onex_G = G;
-            a.onex_target = 0u;
-            a.onex_ticket = ctx->onex_ticket + slot_;
-            a.onex_clear = ctx->onex_ticket + ((slot_ + 128u) & 255u);
-        }
-        // a long chain: the blocked form - one grid-wide sum per FOUR columns (chain_blk.h)
-        if (blk_takes_step(ctx, a, r2) && padded && chain_blk_shape_ok(r2, G, a, fused ? a.offs.nd : 0) && ctx->blk_refused_n != n) {
-            int nsums = 0;
-            // the Gram table: valid when this is the next step of the sequence that owns it; otherwise (a sequence's
-            // first blocked step, a block grown / recycled / written by another entry point since) its rows are
-            // rebuilt from the basis - one panel product per column, once
-            if (!(ctx->blk_V == V && ctx->blk_next == k && ctx->blk_kind == 1)) {
-                double* gt = chain_blk_table(ctx);
-                if (gt == nullptr) return fail(KH_ERR_NOMEM, "chain_blk: no memory for the Gram table");
-                for (int64_t j = 1; j <= k; ++j) {
-                    const int64_t b0 = (j / KH_BLK_BC) * KH_BLK_BC;
-                    if (b0 >= KH_BLK_BC)      // the block before column j's (the kernel takes its dots one block ahead)
-                        KH_TRY(::dot_panel_dev(ctx, V, b0 - KH_BLK_BC, KH_BLK_BC, V->col(j), gt + j * KH_BLK_TW, 0));
-                    if (j > b0) KH_TRY(::dot_panel_dev(ctx, V, b0, j - b0, V->col(j), gt + j * KH_BLK_TW + KH_BLK_BC, 0));
-                }
-                ctx->blk_V = V;
-                ctx->blk_next = k;
-                ctx->blk_kind = 1;
-                ctx->n_blk_rebuild += 1;
-            }
-            e = chain_blk_launch(ctx, r2, G, want_onex, padded, fused ? a.offs.nd : 0, a, V, &nsums);
-            if (e == hipSuccess) {
-                ctx->blk_kind = 1;
-                if (a.debug == 4) ctx->chain_fault = 0;
-                ctx->n_chain += 1;
-                ctx->n_chain_small += 1;
-                ctx->n_chain_blk += 1;
-                ctx->n_chain_onex += want_onex ? 1 : 0;
-                ctx->n_chain_fused += fused ? 1 : 0;
-                ctx->n_dia_mask += (fused && a.dmask != nullptr) ? 1 : 0;
-                ctx->n_chain_lds += 1;
-                ctx->chain_epoch += (unsigned)nsums;
-                if (hpin == nullptr)
-                    KH_HIP(hipMemcpyAsync(ctx->chain_err_pin[slot], ctx->chain_err, sizeof(int), hipMemcpyDeviceToHost,
-                                          ctx->stream));
-                { ctx->wait_tag[slot] = a.donepin != nullptr; return 1; }
-            }
-            (void)hipGetLastError();
-            // refused (occupancy: other kernels resident, fewer compute units ...): remembered for vectors of this length, so
-            // that the steps to come do not rebuild the table - up to 2 k panel products - just to be refused again
-            // (kh_ctx_set("chain_blk", 1) forgets it)
-            ctx->blk_refused_n = n;
-        }
-#define KH_SM_F(R, X, M) (a.offs.nd == 5 ? launch_chain_small<R, false, 5, X, M>(ctx, G, a) : launch_chain_small<R, false, 7, X, M>(ctx, G, a))
-#define KH_SM(R, X)                                                                                              \
-    (fused ? (a.dmask != nullptr ? KH_SM_F(R, X, true) : KH_SM_F(R, X, false))                                   \
-           : (padded ? launch_chain_small<R, false, 0, X>(ctx, G, a) : launch_chain_small<R, true, 0, X>(ctx, G, a)))
-        if (want_onex) e = (r2 == 4) ? KH_SM(4, true) : KH_SM(8, true);
-        else e = (r2 == 4) ? KH_SM(4, false) : KH_SM(8, false);
-#undef KH_SM
-#undef KH_SM_F
-        if (e == hipSuccess) {
-            if (a.debug == 4) ctx->chain_fault = 0;
-            ctx->n_chain += 1;
-            ctx->n_chain_small += 1;
-            ctx->n_chain_onex += want_onex ? 1 : 0;
-            ctx->n_chain_fused += fused ? 1 : 0;
-            ctx->n_dia_mask += (fused && a.dmask != nullptr) ? 1 : 0;
-            ctx->n_chain_lds += 1;          // (the column is used twice from the chip: counted with the LDS / ring family)
-            ctx->chain_epoch += (unsigned)(a.ncol * a.sweeps + 1);
-            if (hpin == nullptr)
-                KH_HIP(hipMemcpyAsync(ctx->chain_err_pin[slot], ctx->chain_err, sizeof(int), hipMemcpyDeviceToHost,
-                                      ctx->stream));
-            { ctx->wait_tag[slot] = a.donepin != nullptr; return 1; }
-        }
-        (void)hipGetLastError();
-    }
-    if (want_onex) {
-        const unsigned slot_ = (unsigned)(ctx->n_chain_onex & 255);
-        a.onex_G = G;
-        a.onex_target = 0u;
-        a.onex_ticket = ctx->onex_ticket + slot_;
-        a.onex_clear = ctx->onex_ticket + ((slot_ + 128u) & 255u);
-        const bool pf_ = (B == V && dg == nullptr && ctx->chain_pf != 0 && ctx->chain_lds != 0);
-#define KH_OX(R)                                                                                                    \
-    (pf_ ? (cplx ? (padded ? launch_chain_onex<R, false, true, true>(ctx, G, a) : launch_chain_onex<R, true, true, true>(ctx, G, a))     \
-                 : (padded ? launch_chain_onex<R, false, false, true>(ctx, G, a) : launch_chain_onex<R, true, false, true>(ctx, G, a)))  \
-         : (cplx ? (padded ? launch_chain_onex<R, false, true, false>(ctx, G, a) : launch_chain_onex<R, true, true, false>(ctx, G, a))   \
-                 : (padded ? launch_chain_onex<R, false, false, false>(ctx, G, a) : launch_chain_onex<R, true, false, false>(ctx, G, a))))
-#define KH_OXF(R) (pf_ ? (a.offs.nd == 5 ? launch_chain_onex_fused<R, 5, true>(ctx, G, a) : launch_chain_onex_fused<R, 7, true>(ctx, G, a)) \
-                      : (a.offs.nd == 5 ? launch_chain_onex_fused<R, 5, false>(ctx, G, a) : launch_chain_onex_fused<R, 7, false>(ctx, G, a)))
-        if (fused) e = (r2 == 4) ? KH_OXF(4) : KH_OXF(8);
-        else e = (r2 == 4) ? KH_OX(4) : KH_OX(8);
-#undef KH_OXF
-#undef KH_OX
-        if (e == hipSuccess) {
-            if (a.debug == 4) ctx->chain_fault = 0;
-            ctx->n_chain += 1;
-            ctx->n_chain_onex += 1;
-            ctx->n_chain_fused += fused ? 1 : 0;
-            ctx->n_dia_mask += (fused && a.dmask != nullptr) ? 1 : 0;
-            ctx->n_chain_lds += pf_ ? 1 : 0;
-            ctx->n_chain_pf += pf_ ? 1 : 0;
-            ctx->chain_epoch += (unsigned)(a.ncol * a.sweeps + 1);
-            if (hpin == nullptr)
-                KH_HIP(hipMemcpyAsync(ctx->chain_err_pin[slot], ctx->chain_err, sizeof(int), hipMemcpyDeviceToHost,
-                                      ctx->stream));
-            { ctx->wait_tag[slot] = a.donepin != nullptr; return 1; }
-        }
-        (void)hipGetLastError();
-    }
-    a.onex_G = 0;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        // k_mgs_chain_lds, mask form: x through the prologue's LDS window when a row's band and the block staged beside it
-        // fit the parked rows the prologue leaves free (all or nothing per launch; x must start a 16-byte row)
-        a.xwin = (fused && !cplx && use_lds && !use_pf && ctx->chain_xwin && a.dmask != nullptr && r2 >= 16 && r2 <= 40 &&
-                  (reinterpret_cast<uintptr_t>(a.xk) & 15u) == 0 &&
-                  xwin_fits(a.offs, a.offs.nd, r2 == 40 ? ChainShapeLds<40>::XWIN_BLOCKS : ChainShapeLds<32>::XWIN_BLOCKS)) ? 1 : 0;
-        if (fused) {
-#define KH_FUSED(R, D)                                                                                   \
-    (use_lds ? (use_pf ? launch_chain_pf<R, false, false, D>(ctx, G, a) : launch_chain_lds<R, false, false, D>(ctx, G, a)) \
-             : launch_chain<R, false, false, D>(ctx, G, a))
-#define KH_FUSED_Z(R, D) (use_lds ? launch_chain_lds<R, false, true, D>(ctx, G, a) : launch_chain<R, false, true, D>(ctx, G, a))
-            if (r2 < 16) return 0;       // (4 / 8 rows: only the Lanczos and the one-XCD kernels have the prologue)
-            if (cplx) {
-                if (r2 == 40) e = (a.offs.nd == 5) ? KH_FUSED_Z(40, 5) : KH_FUSED_Z(40, 7);
-                else if (r2 == 32) e = (a.offs.nd == 5) ? KH_FUSED_Z(32, 5) : KH_FUSED_Z(32, 7);
-                else if (r2 == 24) e = (a.offs.nd == 5) ? KH_FUSED_Z(24, 5) : KH_FUSED_Z(24, 7);
-                else e = (a.offs.nd == 5) ? KH_FUSED_Z(16, 5) : KH_FUSED_Z(16, 7);
-                if (e != hipSuccess) {
-                    (void)hipGetLastError();
-                    return 0;
-                }
-                break;
-            }
-            if (r2 == 48 && use_long) {
-                e = (a.offs.nd == 5) ? launch_chain_long<5>(ctx, G, a) : launch_chain_long<7>(ctx, G, a);
-                if (e != hipSuccess) {       // (e.g. the 128 KB of dynamic LDS were refused: the kernel with both reads from memory)
-                    (void)hipGetLastError();
-                    long_failed = true;
-                    use_long = false;
-                    e = (a.offs.nd == 5) ? launch_chain<48, false, false, 5, 8>(ctx, G, a) : launch_chain<48, false, false, 7, 8>(ctx, G, a);
-                }
-            } else if (r2 == 48) e = (a.offs.nd == 5) ? launch_chain<48, false, false, 5, 8>(ctx, G, a) : launch_chain<48, false, false, 7, 8>(ctx, G, a);
-            else if (r2 == 40) e = (a.offs.nd == 5) ? KH_FUSED(40, 5) : KH_FUSED(40, 7);
-            else if (r2 == 32) e = (a.offs.nd == 5) ? KH_FUSED(32, 5) : KH_FUSED(32, 7);
-            else if (r2 == 24) e = (a.offs.nd == 5) ? KH_FUSED(24, 5) : KH_FUSED(24, 7);
-            else e = (a.offs.nd == 5) ? KH_FUSED(16, 5) : KH_FUSED(16, 7);
-#undef KH_FUSED
-#undef KH_FUSED_Z
-            if (e != hipSuccess) {       // the caller falls back to SpMV + the ordinary chain
-                (void)hipGetLastError();
-                return 0;
-            }
-            break;
-        }
-        if (r2 == 4) e = KH_CHAIN(4);
-        else if (r2 == 8) e = KH_CHAIN(8);
-        else if (r2 == 16) e = KH_CHAIN(16);
-        else if (r2 == 24) e = KH_CHAIN(24);
-        else if (r2 == 32) e = KH_CHAIN(32);
-        else if (r2 == 40) e = KH_CHAIN(40);
-        else if (r2 == 48 && use_long) {
-            e = launch_chain_long<0>(ctx, G, a);
-            if (e != hipSuccess) {
-                (void)hipGetLastError();
-                long_failed = true;
-                use_long = false;
-                e = launch_chain<48, false, false, 0, 8>(ctx, G, a);
-            }
-        }
-        else if (r2 == 48) e = padded ? launch_chain<48, false, false, 0, 8>(ctx, G, a) : launch_chain<48, true, false, 0, 8>(ctx, G, a);
-        else e = padded ? launch_chain<56, false, false, 0, 16>(ctx, G, a) : launch_chain<56, true, false, 0, 16>(ctx, G, a);
-        if (e == hipSuccess || !use_lds) break;
-        (void)hipGetLastError();     // e.g. the 120 KB of dynamic LDS were refused: fall back to the plain kernel
-        lds_failed = true;
-        use_lds = false;
-    }
-#undef KH_CHAIN
-#undef KH_CHAIN_PF
-#undef KH_CHAIN_LDS
-#undef KH_CHAIN_PLAIN
-    if (e != hipSuccess) {
-        // e.g. hipErrorCooperativeLaunchTooLarge: not all workgroups can be co-resident.  A property of this shape
-        // on this device, not of the context: vectors of this length take the per-column kernels from now on
-        (void)hipGetLastError();
-        ctx->chain_refused_n = n;
-        return 0;
-    }
-    if (a.debug == 4) ctx->chain_fault = 0;
-    ctx->n_chain += 1;
-    ctx->n_chain_lds += (use_lds || use_long) ? 1 : 0;
-    ctx->n_chain_long += use_long ? 1 : 0;
-    ctx->n_chain_pf += use_pf ? 1 : 0;
-    ctx->n_chain_fused += fused ? 1 : 0;
-    ctx->n_dia_mask += (fused && a.dmask != nullptr) ? 1 : 0;
-    ctx->n_chain_xwin += a.xwin;
-    ctx->chain_epoch += (unsigned)(a.ncol * a.sweeps + 1);   // one grid reduction per link (complex: both parts in it) + the norm
-    if (hpin == nullptr)      // (otherwise workgroup 0 has written the error word to the pinned slot itself)
-        KH_HIP(hipMemcpyAsync(ctx->chain_err_pin[slot], ctx->chain_err, sizeof(int), hipMemcpyDeviceToHost,
-                              ctx->stream));
-    { ctx->wait_tag[slot] = a.donepin != nullptr; return 1; }
 }
 
 // ---- register-resident panel Gram-Schmidt (k_cgs_dots / k_cgs_update, chain.h) -----------------
@@ -1109,28 +447,9 @@ constexpr int CGS_PSTRIDE = CH_GMAX * (CH_BS / 64);   // wave partials per colum
 template <int R2, bool MASKED, int WL = 0, bool CPLX = false>
 static hipError_t launch_cgs(kh_ctx ctx, int G, CgsArgs& a, bool update) {
     constexpr size_t lds = (size_t)WL * CH_BS * sizeof(double2);
-    if (lds > 0) {
-        static bool attr_done = false;
-        if (!attr_done) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cgs_update<R2, MASKED, WL, CPLX>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e == hipSuccess)
-                e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cgs_dots<R2, MASKED, true, WL, CPLX>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e == hipSuccess)
-                e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cgs_dots<R2, MASKED, false, WL, CPLX>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-            attr_done = true;
-        }
-    }
-    if (update)
-        hipLaunchKernelGGL((k_cgs_update<R2, MASKED, WL, CPLX>), dim3(G), dim3(CH_BS), lds, ctx->stream, a);
-    else if (a.nt_cols)
-        hipLaunchKernelGGL((k_cgs_dots<R2, MASKED, true, WL, CPLX>), dim3(G), dim3(CH_BS), lds, ctx->stream, a);
-    else
-        hipLaunchKernelGGL((k_cgs_dots<R2, MASKED, false, WL, CPLX>), dim3(G), dim3(CH_BS), lds, ctx->stream, a);
-    return hipGetLastError();
+    if (update) return launch_lds<k_cgs_update<R2, MASKED, WL, CPLX>>(ctx, G, CH_BS, lds, a);
+    if (a.nt_cols) return launch_lds<k_cgs_dots<R2, MASKED, true, WL, CPLX>>(ctx, G, CH_BS, lds, a);
+    return launch_lds<k_cgs_dots<R2, MASKED, false, WL, CPLX>>(ctx, G, CH_BS, lds, a);
 }
 
 // One Arnoldi step's panel sweeps with w register-resident.  Returns 1 when done (the norm's wave
@@ -1263,15 +582,7 @@ static int cgs_panel_pass(kh_ctx ctx, kh_vec X, int ncol, double* w, int64_t wld
 template <int R2, bool MASKED>
 static hipError_t launch_dots_x2(kh_ctx ctx, int G, CgsArgs& a) {
     constexpr size_t lds = (size_t)(R2 < 16 ? R2 : 16) * CH_BS * sizeof(double2);      // (the rows of x beyond sixteen: registers)
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cgs_dots<R2, MASKED, false, 0, false, true>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        attr_done = true;
-    }
-    hipLaunchKernelGGL((k_cgs_dots<R2, MASKED, false, 0, false, true>), dim3(G), dim3(CH_BS), lds, ctx->stream, a);
-    return hipGetLastError();
+    return launch_lds<k_cgs_dots<R2, MASKED, false, 0, false, true>>(ctx, G, CH_BS, lds, a);
 }
 
 static __global__ void k_ls_put_column(double* gt, int j, const double* vals) {
@@ -1618,6 +929,7 @@ int kh_ctx_set(kh_ctx ctx, const char* key, int64_t value) {
         ctx->chain_recoveries = 0;          // (an explicit setting starts the count again)
         ctx->chain_clean_steps = 0;
         ctx->chain_refused_n = -1;
+        ctx->chain_lds_failed = ctx->chain_long_failed = 0;
     }
     else if (!strcmp(key, "chain_lds")) ctx->chain_lds = value != 0;
     else if (!strcmp(key, "chain_pf")) ctx->chain_pf = (int)value;
@@ -2924,6 +2236,14 @@ int kh_arnoldi_step_begin(kh_ctx ctx, kh_mat A, kh_proj proj, kh_mat Md, kh_vec 
     // (... nor under the chain kernels with the cross-rank stage: first sweep assigns, like on one GPU)
     if (!want_chain && !want_cgs1 && !(want_blk2 && pd == 0) && !want_chain_xr)
         KH_HIP(hipMemsetAsync(hdev, 0, sizeof(double) * (k + 2 + pd), ctx->stream));
+    // the step as the chain kernels take it (try_chain)
+    ChainStep step;
+    step.V = V; step.B = B; step.P = P;
+    step.w = w; step.wld = W->ld; step.dg = dg;
+    step.k = k; step.start = start; step.sweeps = sweeps;
+    step.presub = presub; step.h_km1 = h_km1; step.h_km1_dev = hk_dev;
+    step.hdev = hdev; step.slot = slot;
+    step.hpin = ctx->hslot_pin[slot]; step.hcount = (int)(k + 2 + pd);
     // 1. operator
     bool fused_chain = false;
     if (A != nullptr) {
@@ -2949,9 +2269,11 @@ int kh_arnoldi_step_begin(kh_ctx ctx, kh_mat A, kh_proj proj, kh_mat Md, kh_vec 
                 }
             }
             ctx->mr_taken = 0;
-            const int rc = try_chain(ctx, V, B, w, W->ld, dg, P, k, start, sweeps, presub, h_km1, hk_dev, hdev,
-                                     slot, false, ctx->hslot_pin[slot], (int)(k + 2 + pd), A, V->col(k),
-                                     job.on ? &job : nullptr);
+            ChainStep cs = step;
+            cs.Afuse = A;
+            cs.xk = V->col(k);
+            cs.mr = job.on ? &job : nullptr;
+            const int rc = try_chain(ctx, cs);
             if (rc < 0) return rc;
             fused_chain = (rc == 1);
             if (ctx->mr_taken) {
@@ -2973,8 +2295,7 @@ int kh_arnoldi_step_begin(kh_ctx ctx, kh_mat A, kh_proj proj, kh_mat Md, kh_vec 
     int nrm_count = grid;     // number of partial sums the norm arrives in
     bool chained = fused_chain;
     if (want_chain && !fused_chain) {
-        const int rc = try_chain(ctx, V, B, w, W->ld, dg, P, k, start, sweeps, presub, h_km1, hk_dev, hdev, slot,
-                                 false, ctx->hslot_pin[slot], (int)(k + 2 + pd));
+        const int rc = try_chain(ctx, step);
         if (rc < 0) return rc;
         chained = (rc == 1);
         if (!chained) {   // not eligible after all: clear the column now, nothing has been accumulated yet

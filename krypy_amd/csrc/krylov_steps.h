@@ -1,6 +1,8 @@
 // The translation units that krylov_hip.hip was split into (round 5) share these helpers of the Arnoldi step:
 //   krylov_hip.hip   context, device blocks, operators (upload, banded copy, SpMV / SpMM launchers), inner products and updates,
-//                    the Arnoldi step (chain / panel / one-reduction launchers, kh_arnoldi_step_begin / _end), the projector
+//                    the Arnoldi step (panel / one-reduction launchers, kh_arnoldi_step_begin / _end), the projector
+//   chain_launch.hip the chain kernels' geometry (chain_geometry, padded_ld), argument block and completion tail, and try_chain:
+//                    which chain kernel takes a step on one GPU (kh_launch.h: the launcher and dispatcher all families share)
 //   cycles.hip       the host loops in C: kh_gmres_cycle, kh_residual, the MINRES recurrences and kh_minres_cycle, the CG step
 //                    and kh_cg_cycle, the caller's drotg
 //   bench_abi.hip    the measurement ABI of bench.py: kh_bench_kernel, kh_bench_arnoldi, kh_chain_trace
@@ -53,11 +55,43 @@ int fetch_scalars(kh_ctx ctx, const double* dev, int64_t count, double* out);
 int push_scalars(kh_ctx ctx, const double* host, int64_t count, double* dev);
 // y = A x for one column; epi / aux select the fused epilogue of the CSR kernels
 int apply_one(kh_ctx ctx, kh_mat A, const double* x, double* y, int epi, const double* aux, double* scal_out, int rmode);
+// the offsets of a banded operator, and - mask form - the values of its diagonals
+inline DiaOffs dia_offs(const kh_mat_s* A) {
+    DiaOffs o;
+    o.nd = A->dia_nd;
+    for (int d = 0; d < KH_DIA_MAX; ++d) o.off[d] = d < A->dia_nd ? A->dia_off[d] : 0;
+    for (int d = 0; d < KH_DIA_CMAX; ++d) o.cst[d] = (A->dmask != nullptr && d < A->dia_nd) ? A->dia_cst[d] : 0.0;
+    return o;
+}
+
+// chain_launch.hip
 bool chain_geometry(kh_ctx ctx, int64_t n, int* r2_out, int* g_out, bool onex = false);
-int try_chain(kh_ctx ctx, kh_vec V, kh_vec B, const double* w, int64_t wld, const double* dg, kh_vec P, int64_t k, int64_t start,
-              int sweeps, bool presub, double h_km1, const double* h_km1_dev, double* hdev, int slot, bool cplx = false,
-              double* hpin = nullptr, int hcount = 0, kh_mat Afuse = nullptr, const double* xk = nullptr,
-              const MinresJob* mr = nullptr);
+int64_t padded_ld(kh_ctx ctx, int64_t n);      // leading dimension of a block of n-vectors (whole chain chunks from 4096 rows on)
+// One Gram-Schmidt step for try_chain: w against columns start .. k of V, `sweeps` times, v_{k+1} (and p_{k+1}) stored, the
+// H column into hdev.
+struct ChainStep {
+    kh_vec V = nullptr;                  // the dots' block ...
+    kh_vec B = nullptr;                  // ... and the updates': P under a Jacobi preconditioner (V = Md P), else V itself
+    const double* w = nullptr;           // A v_k (after the projector of a deflated step); not read when Afuse takes the step
+    int64_t wld = 0;                     // leading dimension of w's block
+    const double* dg = nullptr;          // Jacobi: the diagonal (norm sqrt(<w, dg w>)) ...
+    kh_vec P = nullptr;                  // ... and the block whose column k + 1 is stored beside V's
+    int64_t k = 0, start = 0;
+    int sweeps = 1;
+    bool presub = false;                 // Lanczos: w -= h_km1 * B[:, k - 1] first ...
+    double h_km1 = 0.0;
+    const double* h_km1_dev = nullptr;   // ... with the coefficient still on the device (look-ahead) when not null
+    double* hdev = nullptr;              // the H column on the device
+    int slot = 0;                        // H-column slot: its error word, completion tag and wait_tag
+    bool cplx = false;                   // V, B, w are (re, im) views of complex vectors (zpath.h); hdev holds (re, im) pairs
+    double* hpin = nullptr;              // pinned H slot workgroup 0 copies hcount doubles and the error word to (nullptr: none)
+    int hcount = 0;
+    kh_mat Afuse = nullptr;              // banded operator: w = Afuse * xk in the kernel's prologue (0 is returned when no such
+    const double* xk = nullptr;          // kernel takes the step: the caller runs the SpMV and calls again without Afuse)
+    const MinresJob* mr = nullptr;       // a deferred MINRES update for the Lanczos three-pass kernel to carry (ctx->mr_taken)
+};
+// returns 1 if a chain kernel was launched, 0 if this step is not eligible (the caller uses the link kernels), negative on error
+int try_chain(kh_ctx ctx, const ChainStep& s);
 int try_cgs_reg(kh_ctx ctx, kh_vec V, kh_vec B, double* w, int64_t wld, const double* dg, double* mw, int64_t start, int64_t ncol,
                 int sweeps, bool multi, double* hdev, double* coef, int* nrm_count, bool cplx = false);
 

@@ -3,6 +3,7 @@
 
 #include "kh_internal.h"
 #include "proj_reg.h"
+#include "kh_launch.h"
 
 namespace kh {
 
@@ -33,27 +34,12 @@ void proj_reg_free(kh_ctx ctx) {
 }
 
 template <int R2>
-static hipError_t launch_proj(kh_ctx ctx, int G, ProjRegArgs& a) {
-    static int blocks_per_cu = -1;
-    constexpr size_t lds = ProjRegShape<R2>::LDS_BYTES;
-    if (blocks_per_cu < 0) {
-        if (lds > 0) {
-            hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_proj_reg<R2>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e0 != hipSuccess) return e0;
-        }
-        int nb = 0;
-        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_proj_reg<R2>, CH_BS, lds);
-        if (e != hipSuccess) return e;
-        blocks_per_cu = nb;
-    }
-    if ((int64_t)blocks_per_cu * ctx->ncu < G) return hipErrorCooperativeLaunchTooLarge;      // the sum needs every workgroup resident
-    hipLaunchKernelGGL((k_proj_reg<R2>), dim3(G), dim3(CH_BS), lds, ctx->stream, a);
-    return hipGetLastError();
+static hipError_t launch_proj(kh_ctx ctx, int G, const ProjRegArgs& a) {      // (the sum needs every workgroup resident)
+    return launch_resident<k_proj_reg<R2>>(ctx, G, ResidentShape::chip(ctx, CH_BS, G, ProjRegShape<R2>::LDS_BYTES), a);
 }
 
 // z <- complement projection of z with z register-resident (one launch); ya_dev: d doubles on the device or nullptr.
-// r2 / G: the chain-kernel geometry of vectors of this length (krylov_hip.hip: chain_geometry).  Returns 1 when the
+// r2 / G: the chain-kernel geometry of vectors of this length (chain_launch.hip: chain_geometry).  Returns 1 when the
 // launch was made, 0 when this shape / state is not served (the caller runs the four-launch form), negative on error.
 int proj_reg_apply(kh_ctx ctx, kh_proj p, double* z, int64_t zld, int r2, int G, double* ya_dev) {
     // (ctx->proj_reg_why: why the last call declined - kh_ctx_get "proj_reg_why"; 0 = it ran)
@@ -95,15 +81,7 @@ int proj_reg_apply(kh_ctx ctx, kh_proj p, double* z, int64_t zld, int r2, int G,
     a.epoch0 = ctx->proj_epoch;
     a.err = ctx->proj_err;      // (its own word: a timeout here must not make the chain kernels that follow break out of THEIR waits)
     hipError_t e;
-    switch (r2) {
-        case 16: e = launch_proj<16>(ctx, G, a); break;
-        case 24: e = launch_proj<24>(ctx, G, a); break;
-        case 32: e = launch_proj<32>(ctx, G, a); break;
-        case 40: e = launch_proj<40>(ctx, G, a); break;
-        case 48: e = launch_proj<48>(ctx, G, a); break;
-        case 56: e = launch_proj<56>(ctx, G, a); break;
-        default: return 0;
-    }
+    e = dispatch_int<16, 24, 32, 40, 48, 56>(r2, [&](auto r) { return launch_proj<decltype(r)::value>(ctx, G, a); });
     if (e != hipSuccess) {
         (void)hipGetLastError();
         return 0;

@@ -750,6 +750,12 @@ static int zstep_enqueue(kh_ctx ctx, kh_mat A, kh_vec V, kh_vec W, int64_t wcol,
     double* coef = ctx->scal + ZSC_COEF;
     double2* w = zcolw(W, wcol);
     KH_HIP(hipMemsetAsync(hdev, 0, sizeof(double) * 2 * (k + 2), ctx->stream));
+    ChainStep step;          // the step as the chain kernels take it (try_chain): no preconditioner, no pinned H slot
+    step.V = step.B = V;
+    step.w = W->col(wcol); step.wld = W->ld;
+    step.k = k; step.start = start; step.sweeps = sweeps;
+    step.hdev = hdev; step.slot = slot;
+    step.cplx = true;
     if (A != nullptr) {
         KH_ARG(A->kind >= KH_MAT_ZCSR && A->n_rows == n, "kh_zarnoldi_step: complex operator of matching size needed");
         // a banded complex operator, reference-order Gram-Schmidt, no projector / preconditioner / Lanczos pre-subtraction:
@@ -759,8 +765,13 @@ static int zstep_enqueue(kh_ctx ctx, kh_mat A, kh_vec V, kh_vec W, int64_t wcol,
         const bool lz = (start > 0 && start == k);
         if (gs_mode == KH_GS_MGS && Md == nullptr && proj == nullptr && A->kind == KH_MAT_ZCSR && A->zdia != nullptr &&
             (!lz || h_km1_dev != nullptr || h_km1[1] == 0.0)) {
-            const int rc = try_chain(ctx, V, V, W->col(wcol), W->ld, nullptr, nullptr, k, start, sweeps, lz, lz ? h_km1[0] : 0.0,
-                                     lz ? h_km1_dev : nullptr, hdev, slot, true, nullptr, 0, A, V->col(k));
+            ChainStep cs = step;
+            cs.presub = lz;
+            cs.h_km1 = lz ? h_km1[0] : 0.0;
+            cs.h_km1_dev = lz ? h_km1_dev : nullptr;
+            cs.Afuse = A;
+            cs.xk = V->col(k);
+            const int rc = try_chain(ctx, cs);
             if (rc < 0) return rc;
             if (rc == 1) return 0;
         }
@@ -782,8 +793,7 @@ static int zstep_enqueue(kh_ctx ctx, kh_mat A, kh_vec V, kh_vec W, int64_t wcol,
     // reference-order MGS with w in registers for the whole chain (chain.h, CPLX instantiation):
     // one launch instead of 4 per column
     if (gs_mode == KH_GS_MGS && Md == nullptr) {
-        const int rc = try_chain(ctx, V, V, W->col(wcol), W->ld, nullptr, nullptr, k, start, sweeps, false, 0.0,
-                                 nullptr, hdev, slot, true);
+        const int rc = try_chain(ctx, step);
         if (rc != 0) return rc < 0 ? rc : 0;
     }
     // panel (classical) Gram-Schmidt with w register-resident: two launches per sweep (chain.h, CPLX instantiations)
