@@ -490,6 +490,34 @@ int kh_tri_solve(kh_ctx ctx, kh_tri t, kh_vec X, int64_t xcol, kh_vec Y, int64_t
  * longest row. */
 int kh_tri_info(kh_tri t, int64_t out[8]);
 
+/* ---- Chebyshev polynomial preconditioner -------------------------------------------------------------------------------- */
+/* Both entry points serve the M, Ml, Mr hooks of krypy/linsys.py: z = p(A) r as m steps of the Chebyshev iteration for A z = r
+ * from z = 0, for a Hermitian positive definite A with spectrum in [lmin, lmax] (of Dinv A when scaled).  No reference
+ * counterpart - the reference calls the user's function on host arrays.  The caller computes the m pairs (a_k, b_k) on the host:
+ *   theta = (lmax + lmin) / 2; delta = (lmax - lmin) / 2; sigma = theta / delta; rho_0 = 1 / sigma; (a_0, b_0) = (0, 1 / theta);
+ *   rho_k = 1 / (2 sigma - rho_{k-1}); (a_k, b_k) = (rho_k rho_{k-1}, 2 rho_k / delta).
+ * Per row, every multiply and add rounded on its own (krypy_amd/csrc/cheb.hip):
+ *   step 0:      t = r_i;            [t = t * dinv_i;]  d_i = b_0 * t;                  z_i = d_i
+ *   step k >= 1: t = r_i - (A z)_i;  [t = t * dinv_i;]  d_i = (a_k * d_i) + (b_k * t);  z_i = z_i + d_i
+ * Complex blocks are their (re, im) views of length 2 N; the scalars and dinv (length 2 N, every entry twice) are real. */
+/* M / Ml / Mr hooks, no reference counterpart: one composed step on single columns.  first != 0: step 0 (AZ, Zin, a unused,
+ * may be NULL; d and z_out are only written); else AZ[:, azcol] holds A z_in.  Dinv: a real diagonal kh_mat of the blocks'
+ * length, or NULL.  z_in may be z_out; r, d, z_out (and Az) are different columns.  Rows [n, ld) are not written.  KH_ERR_ARG:
+ * lengths differ, Dinv is no diagonal of that length, columns coincide.  Counter: "n_cheb_update". */
+int kh_cheb_update(kh_ctx ctx, kh_vec AZ, int64_t azcol, kh_vec R, int64_t rcol, kh_mat Dinv, kh_vec D, int64_t dcol, kh_vec Zin,
+                   int64_t zincol, kh_vec Zout, int64_t zoutcol, double a, double b, int first);
+/* M / Ml / Mr hooks, no reference counterpart.  Y[:, ycol + c] = p(A) X[:, xcol + c], c < ncols (one column after the other): all
+ * m steps for a kh_mat operator in one call, m - 1 operator applications per column.  coef: m pairs (a_k, b_k).  S: a
+ * caller-owned scratch block of the same length with at least 2 columns (d and the other half of the z ping-pong; the last
+ * step lands in Y), 3 on the composed path (A z); its contents on entry do not matter.  Steps k >= 1 are ONE launch each - the
+ * SpMV with the step in its epilogue - when A is a real CSR handle without halo, the context has no communicator, and
+ * kh_ctx_set "cheb_fused" (default 1) is on; otherwise kh_apply + the update kernel: the same bits.  KH_ERR_ARG: m < 1; A not
+ * square; lengths differ (also: a real handle on complex blocks or the reverse); Dinv is no real diagonal of the blocks'
+ * length; S has too few columns; X and Y overlap (r is read in every step); S is X or Y.
+ * Counters (kh_ctx_get): "n_cheb_apply" columns applied, "n_cheb_fused" fused launches, "n_cheb_update" update launches. */
+int kh_cheb_apply(kh_ctx ctx, kh_mat A, kh_mat Dinv, int m, const double* coef, kh_vec X, int64_t xcol, kh_vec Y, int64_t ycol,
+                  int64_t ncols, kh_vec S);
+
 /* ---- measurement ----------------------------------------------------------------------- */
 /* bench.py's roofline numbers: average duration (ms) of `reps` back-to-back launches of one hot
  * kernel, HIP events on the context's stream.  which: 0 Gram-Schmidt link (axpy+dot),

@@ -114,6 +114,9 @@ _SIGNATURES = {
     "kh_tri_free": [_H],
     "kh_tri_solve": [_H, _H, _H, _I64, _H, _I64, _I64],
     "kh_tri_info": [_H, _c_int64_p],
+    # Chebyshev polynomial preconditioner (csrc/cheb.hip)
+    "kh_cheb_update": [_H, _H, _I64, _H, _I64, _H, _H, _I64, _H, _I64, _H, _I64, _D, _D, _INT],
+    "kh_cheb_apply": [_H, _H, _H, _INT, _c_double_p, _H, _I64, _H, _I64, _I64, _H],
     "kh_residual": [_H, _H, _H, _I64, _H, _I64, _H, _I64, _c_double_p],
     "kh_gmres_cycle": [_H, _H, _H, _H, _H, _H, _I64, _I64, _I64, _INT, _INT, _c_int64_p, _D, _D, _c_double_p, _I64,
                        _c_double_p, _I64, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_int64_p,
@@ -735,6 +738,33 @@ class Context(object):
             raise BackendError("tri_solve: %s operator on %s blocks" % (t.dtype, X.dtype))
         _check(self._lib, self._lib.kh_tri_solve(self._h, t.handle, X.handle, xcol, Y.handle, ycol, ncols),
                "kh_tri_solve")
+
+    def cheb_update(self, AZ, azcol, R, rcol, Dinv, D, dcol, Zin, zincol, Zout, zoutcol, a, b, first=False):
+        """One composed step of the Chebyshev iteration on single columns (``kh_cheb_update``): ``first`` is step 0
+        (``AZ`` / ``Zin`` may be None), otherwise ``AZ[:, azcol]`` holds ``A z_in``.  ``Dinv``: a real diagonal
+        ``DeviceMatrix`` of the blocks' real length, or None."""
+        _same_dtype("cheb_update", *[B for B in (R, D, Zout, None if first else AZ, None if first else Zin) if B is not None])
+        if Dinv is not None and (Dinv.kind != "diag" or Dinv.dtype != _F64):
+            raise BackendError("cheb_update: Dinv is not a real diagonal operator")
+        h = lambda B: None if B is None else B.handle   # noqa: E731
+        _check(self._lib, self._lib.kh_cheb_update(
+            self._h, None if first else h(AZ), azcol, R.handle, rcol, h(Dinv), D.handle, dcol, None if first else h(Zin),
+            zincol, Zout.handle, zoutcol, float(a), float(b), 1 if first else 0), "kh_cheb_update")
+
+    def cheb_apply(self, A, Dinv, coef, X, xcol, Y, ycol, ncols, S):
+        """``Y[:, ycol:ycol+ncols] = p(A) X[:, xcol:xcol+ncols]``: all ``len(coef)`` steps of the Chebyshev iteration in
+        one call (``kh_cheb_apply``).  ``coef``: the ``(m, 2)`` array of ``(a_k, b_k)``; ``S``: scratch block of the same
+        dtype with 2 columns (3 where the fused kernels do not apply); ``X`` and ``Y`` are different columns."""
+        if (A.dtype == _C128) != _same_dtype("cheb_apply", X, Y, S):
+            raise BackendError("cheb_apply: %s operator on %s blocks" % (A.dtype, X.dtype))
+        if Dinv is not None and (Dinv.kind != "diag" or Dinv.dtype != _F64):
+            raise BackendError("cheb_apply: Dinv is not a real diagonal operator")
+        coef = numpy.ascontiguousarray(coef, dtype=numpy.float64)
+        if coef.ndim != 2 or coef.shape[1] != 2:
+            raise BackendError("cheb_apply: an (m, 2) array of coefficients expected, got shape %s" % (coef.shape,))
+        _check(self._lib, self._lib.kh_cheb_apply(
+            self._h, A.handle, None if Dinv is None else Dinv.handle, coef.shape[0], _dptr(coef), X.handle, xcol, Y.handle,
+            ycol, ncols, S.handle), "kh_cheb_apply")
 
     # ---- numerics (each is one C entry point; complex blocks go to the kh_z* twin) ----
     def apply(self, A, X, xcol, Y, ycol, ncols=1):

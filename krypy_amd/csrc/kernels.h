@@ -440,7 +440,111 @@ __global__ __launch_bounds__(BS) void k_cg_update(int64_t n, double alpha,
 // private 4 MiB L2) walks a contiguous range of row blocks, so the x[i +- nx] neighbours of a
 // stencil row are L2 hits instead of cross-XCD refetches.
 // ------------------------------------------------------------------------------------------
-enum { EPI_NONE = 0, EPI_DOT = 1, EPI_RES = 2 };
+//            EPI_CHEB one step k >= 1 of the Chebyshev iteration (cheb.hip), row-local behind the row sum s = (A z)_i:
+//                     t = r_i - s; [t = t * dinv_i;] d_i = (a * d_i) + (b * t); y_i = z_i + d_i   (x = z, every operation
+//                     rounded on its own).  No reduction (part_out is not touched), no halo.
+enum { EPI_NONE = 0, EPI_DOT = 1, EPI_RES = 2, EPI_CHEB = 3 };
+
+// What EPI_CHEB needs beyond the SpMV's own arguments (x = z_in, y = z_out).  The record lives in DEVICE memory and the kernel
+// finds it behind `aux` (one uniform 40-byte load): the argument lists of k_spmv_stream / k_spmv_dia - and with them every
+// instantiation of the other epilogues - stay what they were.  k_cheb_first / k_cheb_plan write one record per step.
+struct ChebArgs {
+    const double* r;      // the right-hand side of the iteration (read in every step)
+    double* d;            // the direction, updated in place (row-local)
+    const double* dinv;   // optional diagonal scaling (nullptr: none)
+    double a, b;          // this step's pair of coefficients
+};
+
+__device__ __forceinline__ ChebArgs cheb_args(const double* aux) { return *reinterpret_cast<const ChebArgs*>(aux); }
+
+// one row of the step: returns z_out_i, stores d_i (read by the next launch, not by this one: non-temporal)
+__device__ __forceinline__ double cheb_row(const ChebArgs& ch, int64_t i, double zin, double s) {
+    double t = ch.r[i] - s;
+    if (ch.dinv != nullptr) t = t * ch.dinv[i];
+    const double d = (ch.a * ch.d[i]) + (ch.b * t);
+    st_nt(ch.d + i, d);
+    return zin + d;
+}
+
+// ... and an aligned pair of neighbouring rows with 16-byte accesses
+__device__ __forceinline__ double2 cheb_row2(const ChebArgs& ch, int64_t i, double2 zin, double2 s) {
+    const double2 rv = ld_nt2(reinterpret_cast<const double2*>(ch.r + i));
+    const double2 dv = ld_nt2(reinterpret_cast<const double2*>(ch.d + i));
+    double t0 = rv.x - s.x, t1 = rv.y - s.y;
+    if (ch.dinv != nullptr) {
+        const double2 sv = ld_nt2(reinterpret_cast<const double2*>(ch.dinv + i));
+        t0 = t0 * sv.x;
+        t1 = t1 * sv.y;
+    }
+    const double2 d = make_double2((ch.a * dv.x) + (ch.b * t0), (ch.a * dv.y) + (ch.b * t1));
+    st_nt2(reinterpret_cast<double2*>(ch.d + i), d);
+    return make_double2(zin.x + d.x, zin.y + d.y);
+}
+
+// One step of the Chebyshev iteration for A z = r (cheb.hip), the row-local part alone:
+//   az == nullptr (step 0):  t = r_i;          [t = t * dinv_i;]  d_i = b * t;                   z_out_i = d_i
+//   otherwise:               t = r_i - az_i;   [t = t * dinv_i;]  d_i = (a * d_i) + (b * t);     z_out_i = z_in_i + d_i
+// every multiply and add rounded on its own.  Step 0 reads neither d nor z_in.  z_in may be z_out (row-local).
+__device__ __forceinline__ void cheb_update_rows(int64_t n, const double* __restrict__ az, const double* __restrict__ r,
+                                                 const double* __restrict__ dinv, double* __restrict__ d, const double* z_in,
+                                                 double* z_out, double a, double b) {
+    const int64_t stride = (int64_t)gridDim.x * BS;
+    for (int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x; i < n; i += stride) {
+        if (az == nullptr) {
+            double t = r[i];
+            if (dinv != nullptr) t = t * dinv[i];
+            const double dv = b * t;
+            st_nt(d + i, dv);
+            st_nt(z_out + i, dv);
+        } else {
+            double t = r[i] - az[i];
+            if (dinv != nullptr) t = t * dinv[i];
+            const double dv = (a * d[i]) + (b * t);
+            const double zv = z_in[i] + dv;
+            st_nt(d + i, dv);
+            st_nt(z_out + i, zv);
+        }
+    }
+}
+
+static __global__ __launch_bounds__(BS) void k_cheb_update(int64_t n, const double* __restrict__ az,
+                                                    const double* __restrict__ r,
+                                                    const double* __restrict__ dinv, double* __restrict__ d,
+                                                    const double* z_in, double* z_out, double a, double b) {
+    cheb_update_rows(n, az, r, dinv, d, z_in, z_out, a, b);
+}
+
+// The records of the fused steps (EPI_CHEB reads them from device memory): tab[k0 + t] = (r, d, dinv, ab[2 t], ab[2 t + 1]).
+constexpr int KH_CHEB_PLAN = 16;      // records one launch writes
+struct ChebPlan {
+    const double* r;
+    double* d;
+    const double* dinv;
+    int k0, count;
+    double ab[2 * KH_CHEB_PLAN];
+};
+
+__device__ __forceinline__ void cheb_plan_write(ChebArgs* __restrict__ tab, const ChebPlan& p) {
+    if (blockIdx.x == 0 && (int)threadIdx.x < p.count) {
+        ChebArgs rec;
+        rec.r = p.r;
+        rec.d = p.d;
+        rec.dinv = p.dinv;
+        rec.a = p.ab[2 * threadIdx.x];
+        rec.b = p.ab[2 * threadIdx.x + 1];
+        tab[p.k0 + threadIdx.x] = rec;
+    }
+}
+
+// step 0 of a fused application, and the records of its first KH_CHEB_PLAN fused steps on the way (b0: step 0's coefficient)
+static __global__ __launch_bounds__(BS) void k_cheb_first(int64_t n, double* __restrict__ z_out, double b0,
+                                                   ChebArgs* __restrict__ tab, ChebPlan p) {
+    cheb_plan_write(tab, p);
+    cheb_update_rows(n, nullptr, p.r, p.dinv, p.d, nullptr, z_out, 0.0, b0);
+}
+
+// ... further records (more than KH_CHEB_PLAN + 1 steps)
+static __global__ __launch_bounds__(BS) void k_cheb_plan(ChebArgs* __restrict__ tab, ChebPlan p) { cheb_plan_write(tab, p); }
 
 __device__ __forceinline__ int xcd_remap(int b, int nblk) {
     const int q = nblk >> 3, r = nblk & 7;
@@ -538,6 +642,7 @@ __global__ __launch_bounds__(BS) void k_spmv_stream(const int32_t* __restrict__ 
                 s = aux[r] - s;
                 acc = fma(s, s, acc);
             }
+            if constexpr (EPI == EPI_CHEB) s = cheb_row(cheb_args(aux), r, x[r], s);
             st_nt(y + r, s);
             if (EPI == EPI_DOT) acc = fma(aux[r], s, acc);
         }
@@ -555,11 +660,12 @@ __global__ __launch_bounds__(BS) void k_spmv_stream(const int32_t* __restrict__ 
                 s = aux[r0] - s;
                 acc = s * s;
             }
+            if constexpr (EPI == EPI_CHEB) s = cheb_row(cheb_args(aux), r0, x[r0], s);
             y[r0] = s;
             if (EPI == EPI_DOT) acc = aux[r0] * s;
         }
     }
-    if (EPI != EPI_NONE) {
+    if (EPI != EPI_NONE && EPI != EPI_CHEB) {
         const double r = block_sum(acc, sm);
         if (threadIdx.x == 0) part_out[part_off + blockIdx.x] = r;
     }
@@ -752,6 +858,7 @@ __global__ __launch_bounds__(BS) void k_spmv_dia(DiaOffs o, const double* __rest
                                                  double* __restrict__ part_out,
                                                  int blk_lo = 0x7fffffff, int blk_skip = 0, int part_off = 0,
                                                  XhArgs xh = XhArgs()) {
+    static_assert(EPI != EPI_CHEB || (!HALO && !XH), "EPI_CHEB has no halo form");
     __shared__ double sm[8];
     int lb, pslot = blockIdx.x;
     if constexpr (XH) {
@@ -887,6 +994,20 @@ __global__ __launch_bounds__(BS) void k_spmv_dia(DiaOffs o, const double* __rest
                 acc = fma(aux[r], v0, acc);
                 acc = fma(aux[r + 1], v1, acc);
             }
+            if constexpr (EPI == EPI_CHEB) {
+                const ChebArgs ch = cheb_args(aux);
+                // r, d, dinv and x allow 16-byte accesses to a row pair (y does: the launcher)
+                const bool chal = xal && ((reinterpret_cast<uintptr_t>(ch.r) | reinterpret_cast<uintptr_t>(ch.d) |
+                                           reinterpret_cast<uintptr_t>(ch.dinv)) & 15) == 0;
+                if (chal) {
+                    const double2 z2 = cheb_row2(ch, r, *reinterpret_cast<const double2*>(x + r), make_double2(v0, v1));
+                    v0 = z2.x;
+                    v1 = z2.y;
+                } else {
+                    v0 = cheb_row(ch, r, x[r], v0);
+                    v1 = cheb_row(ch, r + 1, x[r + 1], v1);
+                }
+            }
             st_nt2(reinterpret_cast<double2*>(y + r), make_double2(v0, v1));
         } else if (r < n) {
             if (EPI == EPI_RES) {
@@ -894,10 +1015,11 @@ __global__ __launch_bounds__(BS) void k_spmv_dia(DiaOffs o, const double* __rest
                 acc = fma(v0, v0, acc);
             }
             if (EPI == EPI_DOT) acc = fma(aux[r], v0, acc);
+            if constexpr (EPI == EPI_CHEB) v0 = cheb_row(cheb_args(aux), r, x[r], v0);
             y[r] = v0;
         }
     }
-    if (EPI != EPI_NONE) {
+    if (EPI != EPI_NONE && EPI != EPI_CHEB) {
         const double r = block_sum(acc, sm);
         if (threadIdx.x == 0) part_out[part_off + pslot] = r;
     }

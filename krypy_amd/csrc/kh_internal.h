@@ -100,6 +100,11 @@ struct kh_ctx_s {
     // sparse triangular solves (tri.hip): levels of at most tri_narrow_rows rows share a one-workgroup launch (read by kh_tri_create)
     int64_t tri_narrow_rows = 1024;
     int64_t n_tri_solve = 0, n_tri_wide = 0, n_tri_narrow = 0;   // columns solved; launches of k_tri_wide / k_tri_narrow
+    // Chebyshev polynomial preconditioner (cheb.hip): steps k >= 1 as ONE launch, the SpMV with the step in its epilogue
+    int cheb_fused = 1;
+    void* cheb_tab = nullptr;        // device records of one application's fused steps (kernels.h: ChebArgs), cheb_tab_cap of them
+    int64_t cheb_tab_cap = 0;
+    int64_t n_cheb_apply = 0, n_cheb_fused = 0, n_cheb_update = 0;   // columns applied; fused launches; launches of k_cheb_update
     int64_t n_spmm = 0;     // panel applications of a CSR operator that streamed the matrix once
     int chain_spmv = 1;     // banded operators: w = A v_k in the chain kernel's prologue (KRYPY_AMD_CHAIN_SPMV)
     int chain_pf = 1;       // ... and keep HBM busy through the update phase (k_mgs_chain_pf; KRYPY_AMD_CHAIN_PF)

@@ -857,6 +857,7 @@ int kh_ctx_destroy(kh_ctx ctx) {
         if (ctx->hev[s]) (void)hipEventDestroy(ctx->hev[s]);
     }
     (void)hipFree(ctx->cgs_part);
+    (void)hipFree(ctx->cheb_tab);
     (void)hipFree(ctx->chain_gran);
     (void)hipFree(ctx->chain_xcc);
     (void)hipFree(ctx->onex_ticket);
@@ -1001,6 +1002,7 @@ int kh_ctx_set(kh_ctx ctx, const char* key, int64_t value) {
         KH_ARG(value >= 0, "kh_ctx_set: tri_narrow_rows < 0");
         ctx->tri_narrow_rows = value;
     }
+    else if (!strcmp(key, "cheb_fused")) ctx->cheb_fused = value ? 1 : 0;     // kh_cheb_apply: the fused epilogue where it applies
     else if (!strcmp(key, "chain_epoch")) ctx->chain_epoch = (unsigned)value;      // tests: bring the epoch counter of the grid-wide sums near its wrap
     else if (!strcmp(key, "chain_debug")) ctx->chain_debug = (int)value;    // measurement: phases switched off (garbage results)
     else return fail(KH_ERR_ARG, "kh_ctx_set: unknown key '%s'", key);
@@ -1080,6 +1082,10 @@ int kh_ctx_get(kh_ctx ctx, const char* key, int64_t* value) {
     else if (!strcmp(key, "n_tri_solve")) *value = ctx->n_tri_solve;
     else if (!strcmp(key, "n_tri_wide")) *value = ctx->n_tri_wide;
     else if (!strcmp(key, "n_tri_narrow")) *value = ctx->n_tri_narrow;
+    else if (!strcmp(key, "cheb_fused")) *value = ctx->cheb_fused;
+    else if (!strcmp(key, "n_cheb_apply")) *value = ctx->n_cheb_apply;
+    else if (!strcmp(key, "n_cheb_fused")) *value = ctx->n_cheb_fused;
+    else if (!strcmp(key, "n_cheb_update")) *value = ctx->n_cheb_update;
     else if (!strcmp(key, "chain_epoch")) *value = ctx->chain_epoch;
     else if (!strcmp(key, "n_epoch_wraps")) *value = ctx->n_epoch_wraps;
     else return fail(KH_ERR_ARG, "kh_ctx_get: unknown key '%s'", key);

@@ -31,7 +31,7 @@ __all__ = [
     "ZeroLinearOperator", "Projection", "arnoldi", "arnoldi_res", "find_common_dtype",
     "get_linearoperator", "inner", "ip_euclid", "norm", "norm_squared", "orthonormality", "qr",
     "shape_vec", "shape_vecs", "DVec", "Timer", "Timings", "TimedLinearOperator", "ritz",
-    "hegedus", "angles", "TriangularSolveOperator", "ilu_operator",
+    "hegedus", "angles", "TriangularSolveOperator", "ilu_operator", "ChebyshevOperator", "chebyshev_operator",
 ]
 
 
@@ -1010,6 +1010,186 @@ def ilu_operator(ilu):
     if not numpy.array_equal(perm_c, ar):
         op = MatrixLinearOperator(scipy.sparse.csr_matrix((numpy.ones(n), (ar, perm_c)), shape=(n, n))) * op
     return op
+
+
+def chebyshev_coefficients(lmin, lmax, degree):
+    """The ``(degree, 2)`` float64 array of ``(a_k, b_k)`` of the Chebyshev iteration on ``[lmin, lmax]``, in Python floats:
+    ``theta = (lmax + lmin) / 2; delta = (lmax - lmin) / 2; sigma = theta / delta; rho_0 = 1 / sigma; (a_0, b_0) = (0, 1 / theta);
+    rho_k = 1 / (2 sigma - rho_{k-1}); (a_k, b_k) = (rho_k rho_{k-1}, 2 rho_k / delta)``."""
+    lmin, lmax = float(lmin), float(lmax)
+    theta = (lmax + lmin) / 2
+    delta = (lmax - lmin) / 2
+    sigma = theta / delta
+    rho = 1 / sigma
+    coef = numpy.zeros((degree, 2))
+    coef[0] = (0.0, 1 / theta)
+    for k in range(1, degree):
+        rho_new = 1 / (2 * sigma - rho)
+        coef[k] = (rho_new * rho, 2 * rho_new / delta)
+        rho = rho_new
+    return coef
+
+
+class ChebyshevOperator(LinearOperator):
+    """The Chebyshev polynomial preconditioner ``M = p(A)``: ``z = M r`` is ``degree`` steps of the Chebyshev iteration for
+    ``A z = r`` from ``z = 0`` (``Context.cheb_apply`` / ``cheb_update``), for a Hermitian positive definite ``A`` whose
+    spectrum lies in ``[lmin, lmax]``.  ``M`` is Hermitian positive definite too, so it serves ``Cg`` and ``Minres`` as ``M``
+    and ``Gmres`` as ``M``, ``Ml`` or ``Mr``; it costs ``degree - 1`` applications of ``A`` and consists of operator
+    applications and row-local updates only - no factorisation, and it works on a sharded operator.  The reference has no
+    counterpart (it takes any callable).
+
+    :param A: a matrix, a ``MatrixLinearOperator`` / ``DeviceOperator`` (all steps in one call of the library, one launch per
+        step where the fused kernels apply), or any other ``LinearOperator`` with a device action (one ``A._apply_dev`` and one
+        ``cheb_update`` per step).
+    :param lmax, lmin: bounds of the spectrum, ``0 < lmin < lmax``; ``lmin`` defaults to ``lmax / ratio``.
+    :param degree: number of steps ``m >= 1``.
+    :param scale: None, ``"jacobi"`` (the diagonal of a matrix ``A``) or a 1-D array of positive reals ``s``: the iteration
+        then runs for ``diag(1/s) A`` and the bounds refer to that operator.
+
+    Per row, every operation rounded on its own: step 0 ``t = r; [t = t * dinv;] d = b_0 * t; z = d``, step k
+    ``t = r - A z; [t = t * dinv;] d = (a_k * d) + (b_k * t); z = z + d`` with ``coefficients[k] = (a_k, b_k)``.
+    ``_device_matrix()`` stays None: the solvers treat it as an external operator, applied once per step."""
+
+    def __init__(self, A, lmax, lmin=None, degree=4, ratio=30.0, scale=None):
+        mat = None
+        if isinstance(A, LinearOperator):
+            op = A
+            if isinstance(A, MatrixLinearOperator) and not isinstance(A, DeviceOperator):
+                mat = A._A
+        else:
+            if not _is_sparse(A):
+                A = numpy.asarray(A)
+                if A.ndim != 2:
+                    raise ArgumentError("a matrix expected, got an array of shape %s" % (A.shape,))
+            mat = A
+            if A.shape[0] == A.shape[1] and A.dtype not in (numpy.dtype(numpy.float64), numpy.dtype(numpy.complex128)):
+                mat = A.astype(_bdt(A.dtype))          # the device works in fp64 / c128 and the operator says so
+            op = MatrixLinearOperator(mat)
+        if op.shape[0] != op.shape[1]:
+            raise ArgumentError("a square operator expected, got shape %s" % (op.shape,))
+        if not _isintlike(degree) or degree < 1:
+            raise ArgumentError("degree %r: an integer >= 1 expected" % (degree,))
+        if lmin is None:
+            lmin = float(lmax) / float(ratio)
+        lmax, lmin = float(lmax), float(lmin)
+        if not (0.0 < lmin < lmax and numpy.isfinite(lmax)):
+            raise ArgumentError("bounds 0 < lmin < lmax expected, got lmin = %r, lmax = %r" % (lmin, lmax))
+        n = op.shape[0]
+        dinv = None
+        if scale is not None:
+            if isinstance(scale, str):
+                if scale != "jacobi":
+                    raise ArgumentError("scale %r: None, 'jacobi' or a 1-D array expected" % (scale,))
+                if mat is None:
+                    raise ArgumentError("scale='jacobi' needs a matrix: this operator has no diagonal to read")
+                s = mat.diagonal() if _is_sparse(mat) else numpy.diagonal(numpy.asarray(mat))
+            else:
+                s = scale
+            s = numpy.asarray(s)
+            if s.ndim != 1 or s.shape[0] != n:
+                raise ArgumentError("a scale of shape (%d,) expected, got %s" % (n, s.shape))
+            if s.dtype.kind == "c":
+                if numpy.any(s.imag != 0):
+                    raise ArgumentError("the scale has a complex entry")
+                s = s.real
+            s = numpy.asarray(s, dtype=float)
+            if not numpy.all(s > 0) or not numpy.all(numpy.isfinite(s)):
+                raise ArgumentError("the scale has an entry that is not a positive finite number")
+            dinv = 1.0 / s
+        super(ChebyshevOperator, self).__init__((n, n), _bdt(op.dtype), self._dot, self._dot)
+        self._op, self._matrix_path = op, isinstance(op, MatrixLinearOperator)
+        self.degree, self.lmin, self.lmax = int(degree), lmin, lmax
+        self.coefficients = chebyshev_coefficients(lmin, lmax, self.degree)
+        self.dinv = dinv
+        self._dinv_dev = {}
+        self._blocks = {}
+
+    @property
+    def adj(self):
+        """The operator itself: ``p(A)`` with real coefficients is Hermitian when ``A`` is."""
+        return self
+
+    def _dinv_image(self, ctx, dtype):
+        """``dinv`` as a real device diagonal: of length N for real blocks, 2N (every entry twice) for the (re, im) view."""
+        if self.dinv is None:
+            return None
+        key = (id(ctx), _bdt(dtype).kind)
+        dm = self._dinv_dev.get(key)
+        if dm is None:
+            dm = self._dinv_dev[key] = ctx.diag(numpy.repeat(self.dinv, 2) if _is_c(dtype) else self.dinv)
+        return dm
+
+    def _cheb_scratch(self, ctx, dtype):
+        """Three columns per context and block dtype: d, the other half of the z ping-pong, A z."""
+        key = (id(ctx), _bdt(dtype).kind)
+        b = self._blocks.get(key)
+        if b is None:
+            b = self._blocks[key] = ctx.alloc(self.shape[0], 3, dtype=_bdt(dtype))
+        return b
+
+    def _apply_dev(self, X, xcol, Y, ycol, ncols=1):
+        if _is_c(self.dtype) and not _is_c(X.dtype):
+            raise LinearOperatorError("complex Chebyshev operator applied to a real device block")
+        ctx = X.ctx
+        S = self._cheb_scratch(ctx, X.dtype)
+        dinv = self._dinv_image(ctx, X.dtype)
+        if X is Y and xcol < ycol + ncols and ycol < xcol + ncols:      # r is read in every step: it moves out of the result's way
+            T = ctx.alloc(X.n, ncols, dtype=X.dtype)
+            T.copy_from(0, X, xcol, ncols)
+            X, xcol = T, 0
+        if self._matrix_path:
+            dm = self._op._device_matrix(ctx, X.dtype)
+            if dm.kind != "diag":                  # (a diagonal A goes the general way: kh_cheb_apply takes CSR and dense handles)
+                ctx.cheb_apply(dm, dinv, self.coefficients, X, xcol, Y, ycol, ncols, S)
+                return
+        coef, m = self.coefficients, self.degree
+        for c in range(ncols):
+            # z after step k lives in Y when m - 1 - k is even, else in the scratch: the last step lands in Y
+            where = [(Y, ycol + c) if (m - 1 - k) % 2 == 0 else (S, 1) for k in range(m)]
+            ctx.cheb_update(None, 0, X, xcol + c, dinv, S, 0, None, 0, where[0][0], where[0][1], 0.0, coef[0, 1], first=True)
+            for k in range(1, m):
+                (Zi, zi), (Zo, zo) = where[k - 1], where[k]
+                self._op._apply_dev(Zi, zi, S, 2, 1)
+                ctx.cheb_update(S, 2, X, xcol + c, dinv, S, 0, Zi, zi, Zo, zo, coef[k, 0], coef[k, 1])
+
+    def _dot(self, X):
+        X = numpy.asarray(X)
+        ctx = _hip.get_context()
+        dt = _bdt(self.dtype, X.dtype)
+        Xd = ctx.upload(X, dtype=dt)
+        Yd = ctx.alloc(self.shape[0], X.shape[1], dtype=dt)
+        self._apply_dev(Xd, 0, Yd, 0, X.shape[1])
+        return numpy.ascontiguousarray(Yd.download())
+
+    def __repr__(self):
+        return "<%dx%d ChebyshevOperator (degree %d on [%g, %g]%s) with dtype=%s>" % (
+            self.shape[0], self.shape[1], self.degree, self.lmin, self.lmax, "" if self.dinv is None else ", scaled", self.dtype)
+
+
+def chebyshev_operator(A, degree=4, steps=10, boost=1.1, ratio=30.0, scale=None, seed=0):
+    """A :class:`ChebyshevOperator` with an estimated upper bound: ``lmax = boost *`` the largest Ritz value of ``steps``
+    Lanczos steps (``Arnoldi(..., ortho='lanczos')`` on the device, the eigenvalues of the tridiagonal matrix on the host) on
+    ``A``, or on ``D^{-1/2} A D^{-1/2}`` when scaled (the spectrum of ``D^{-1} A``), from a seeded normal start vector;
+    ``lmin = lmax / ratio``.  The estimate is kept as ``lmax_estimate``."""
+    probe = ChebyshevOperator(A, 1.0, degree=degree, ratio=ratio, scale=scale)       # the argument checks, op and dinv
+    op = probe._op
+    n = op.shape[0]
+    if probe.dinv is not None:
+        Dh = MatrixLinearOperator(scipy.sparse.diags(numpy.sqrt(probe.dinv)).tocsr())
+        op = Dh * op * Dh
+    v = numpy.random.default_rng(seed).standard_normal((n, 1))
+    if _is_c(op.dtype):
+        v = v.astype(complex)
+    arn = Arnoldi(op, v, maxiter=min(int(steps), n), ortho="lanczos")
+    while arn.iter < arn.maxiter and not arn.invariant:
+        arn.advance()
+    k = arn.iter
+    H = numpy.asarray(arn.H[:k, :k])
+    theta = numpy.linalg.eigvalsh((H + H.conj().T) / 2)
+    lmax = float(boost) * float(theta[-1])
+    out = ChebyshevOperator(A, lmax, degree=degree, ratio=ratio, scale=scale)
+    out.lmax_estimate = lmax
+    return out
 
 
 class Timer(list):
