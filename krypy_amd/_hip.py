@@ -776,8 +776,10 @@ class Context(object):
     def dot_panel(self, V, j0, ncols, W, wcol):
         if _same_dtype("dot_panel", V, W):
             out = numpy.empty(max(ncols, 1), dtype=numpy.complex128)
-            _check(self._lib, self._lib.kh_zdot_panel(self._h, V.handle, j0, ncols, W.handle, wcol,
-                                                      _dptr(out)), "kh_zdot_panel")
+            for c0 in range(0, max(ncols, 1), 512):       # the complex entry point takes at most 512 columns per call
+                m = min(512, ncols - c0)
+                _check(self._lib, self._lib.kh_zdot_panel(self._h, V.handle, j0 + c0, m, W.handle, wcol,
+                                                          _dptr(out[c0:])), "kh_zdot_panel")
             return out[:ncols]
         out = numpy.empty(max(ncols, 1), dtype=numpy.float64)
         for c0 in range(0, max(ncols, 1), 1024):      # the C entry point takes at most 1024 columns per call
@@ -809,8 +811,10 @@ class Context(object):
     def axpy_panel(self, V, j0, ncols, h, W, wcol):
         if _same_dtype("axpy_panel", V, W):
             h, hp = _zarr(numpy.asarray(h).reshape(-1))
-            _check(self._lib, self._lib.kh_zaxpy_panel(self._h, V.handle, j0, ncols, hp, W.handle,
-                                                       wcol), "kh_zaxpy_panel")
+            for c0 in range(0, max(ncols, 1), 512):       # at most 512 complex columns per call, left to right
+                m = min(512, ncols - c0)
+                _check(self._lib, self._lib.kh_zaxpy_panel(self._h, V.handle, j0 + c0, m, _dptr(h[c0:]), W.handle,
+                                                           wcol), "kh_zaxpy_panel")
             return
         h = _real_coeffs(h, "axpy_panel").reshape(-1)
         for c0 in range(0, max(ncols, 1), 1024):      # at most 1024 columns per call, left to right
@@ -922,6 +926,9 @@ class Context(object):
 
     def proj_apply_complement(self, proj, A, acol, Z, zcol, want_ya=False):
         cplx = getattr(proj, "cplx", False)
+        if _same_dtype("proj_apply_complement", A, Z) != bool(cplx):
+            raise BackendError("proj_apply_complement: a %s projector for %s vectors" % (
+                "complex" if cplx else "real", A.dtype))
         ya = numpy.empty(proj.d, dtype=numpy.complex128 if cplx else numpy.float64) if want_ya else None
         fn = self._lib.kh_zproj_apply_complement if cplx else self._lib.kh_proj_apply_complement
         _check(self._lib, fn(self._h, proj.handle, A.handle, acol, Z.handle, zcol,

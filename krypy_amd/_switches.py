@@ -151,6 +151,8 @@ SWITCHES = [
      "1: the WHOLE GPU suite through the multi-rank code path on a 1-rank communicator (`tests/conftest.py`)"),
     ("KRYPY_AMD_PARITY_LOG", "unset", "test", None,
      "file the full-size parity tests append their measured deviations to (`profiles/r05_fullsize_parity.log` comes from such a run)"),
+    ("KRYPY_AMD_PROJ_LOG", "unset", "test", None,
+     "file the projector tests (`tests/test_gpu_proj.py`) append one line per case to: launch counters, measured error, bar and their ratio per quantity (`profiles/proj_ref_gpu.log` comes from such a run)"),
     ("KRYPY_AMD_FULLSIZE_ORACLE", "0", "test", None,
      "1: `tests/test_oracle_golden.py` also runs the CPU oracle at N = 10^7 / n = 32768 against the full-size fixtures (ten minutes)"),
 ]

@@ -175,6 +175,7 @@ struct kh_ctx_s {
     int64_t n_proj_recovered = 0;
     int proj_reg_why = -1;           // why proj_reg_apply declined last time (1: switches / shape of the projector, 2: short vector, 3: blocks
                                      // not padded alike, 4: the launch failed; 0: it ran)
+    int proj_reg_rows = 0;           // rows per lane (16 ... 56) of the one-launch projector in the last projector call, real or complex; 0 when it declined (kh_ctx_get "proj_reg_rows")
     int proj_panel = 1;              // ... or, on N ranks, its passes through the register-resident panel kernels (KRYPY_AMD_PROJ_PANEL)
     int64_t n_proj_panel = 0;        // sweeps that took them
     int64_t n_cycle_steps = 0;   // GMRES iterations recorded by kh_gmres_cycle

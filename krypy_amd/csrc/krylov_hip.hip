@@ -1066,6 +1066,7 @@ int kh_ctx_get(kh_ctx ctx, const char* key, int64_t* value) {
     else if (!strcmp(key, "n_proj_reg")) *value = ctx->n_proj_reg;
     else if (!strcmp(key, "n_proj_recovered")) *value = ctx->n_proj_recovered;
     else if (!strcmp(key, "proj_reg_why")) *value = ctx->proj_reg_why;
+    else if (!strcmp(key, "proj_reg_rows")) *value = ctx->proj_reg_rows;
     else if (!strcmp(key, "proj_panel")) *value = ctx->proj_panel;
     else if (!strcmp(key, "n_proj_panel")) *value = ctx->n_proj_panel;
     else if (!strcmp(key, "n_lowsync")) *value = ctx->n_lowsync;
@@ -1893,6 +1894,8 @@ static int dot_panel_dev(kh_ctx ctx, kh_vec V, int64_t j0, int64_t ncols, const 
 // z = complement projection of z (in place); ya_dev (d doubles on the device) gets <Y, z_in>
 static int proj_apply_dev(kh_ctx ctx, kh_proj p, double* z, double* ya_dev, int64_t zld = 0) {
     const int d = (int)p->d;
+    ctx->proj_reg_rows = 0;      // (a vector chain_geometry declines never reaches proj_reg_apply: reason 2, no shape for
+    ctx->proj_reg_why = 2;       // this length)
     // long vectors on one GPU: both sweeps in ONE launch with z in registers (proj_reg.h)
     if (zld > 0) {
         int r2 = 0, G = 0;
@@ -2159,6 +2162,7 @@ int kh_arnoldi_step_begin(kh_ctx ctx, kh_mat A, kh_proj proj, kh_mat Md, kh_vec 
     KH_ARG(sweeps >= 1 && sweeps <= 4, "kh_arnoldi_step: sweeps=%d", sweeps);
     // sized for the whole basis up front: never reallocated while steps of this basis are in flight
     const int64_t pd = proj ? proj->d : 0;
+    KH_ARG(proj == nullptr || !proj->cplx, "kh_arnoldi_step: a complex projector (kh_zproj_create) goes to kh_zarnoldi_step_begin_proj");
     KH_ARG(proj == nullptr || (proj->W->n == V->n && A != nullptr), "kh_arnoldi_step: projector needs A and length N");
     KH_TRY(ensure_hcap(ctx, std::max<int64_t>(k + 2, V->ncols + 1) + pd));
     // Md: the Jacobi preconditioner (diagonal; V = Md P), or - same recurrence with the roles of the blocks swapped,
@@ -2601,6 +2605,7 @@ int kh_proj_free(kh_proj p) {
 int kh_proj_apply_complement(kh_ctx ctx, kh_proj p, kh_vec A, int64_t acol, kh_vec Z, int64_t zcol,
                              double* ya_out) {
     KH_ARG(ctx && p, "kh_proj_apply_complement: NULL");
+    KH_ARG(!p->cplx, "kh_proj_apply_complement: a complex projector (kh_zproj_create) goes to kh_zproj_apply_complement");
     KH_TRY(check_vec(A, acol, 1, "kh_proj_apply_complement(a)"));
     KH_TRY(check_vec(Z, zcol, 1, "kh_proj_apply_complement(z)"));
     KH_ARG(A->n == p->W->n && Z->n == A->n, "kh_proj_apply_complement: length mismatch");

@@ -44,6 +44,7 @@ static hipError_t launch_proj(kh_ctx ctx, int G, const ProjRegArgs& a) {      //
 int proj_reg_apply(kh_ctx ctx, kh_proj p, double* z, int64_t zld, int r2, int G, double* ya_dev) {
     // (ctx->proj_reg_why: why the last call declined - kh_ctx_get "proj_reg_why"; 0 = it ran)
     ctx->proj_reg_why = 1;
+    ctx->proj_reg_rows = 0;
     if (!ctx->proj_reg || !ctx->chain_enabled || kh_multi(ctx) || p->cplx || p->d < 1 || p->d > PR_NV || p->iterations < 1) return 0;
     ctx->proj_reg_why = 2;
     if (r2 < 16 || G > CH_GMAX / 2 || G > 256) return 0;       // (short vectors: the four launches are latency-bound either way)
@@ -87,6 +88,7 @@ int proj_reg_apply(kh_ctx ctx, kh_proj p, double* z, int64_t zld, int r2, int G,
         return 0;
     }
     ctx->proj_reg_why = 0;
+    ctx->proj_reg_rows = r2;
     ctx->proj_epoch += (unsigned)p->iterations;
     ctx->n_proj_reg += 1;
     if (ctx->proj_fault) {          // tests: what a timed-out sum leaves behind - the error word set, garbage in z

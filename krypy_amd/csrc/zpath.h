@@ -716,6 +716,8 @@ __global__ __launch_bounds__(BS) void k_zsmall_matvec(int d, const double2* __re
 // ya_dev (d complex numbers) gets <Y, z_in>
 static int zproj_apply_dev(kh_ctx ctx, kh_proj p, double2* z, double* ya_dev) {
     const int d = (int)p->d;
+    ctx->proj_reg_why = 1;       // (the one-launch kernel serves no complex projector: what proj_reg_apply would answer)
+    ctx->proj_reg_rows = 0;
     for (int it = 0; it < p->iterations; ++it) {
         KH_TRY(zdot_dev(ctx, p->W, 0, d, z, p->c0));          // (all-reduced over the ranks inside)
         if (it == 0 && ya_dev != nullptr)
