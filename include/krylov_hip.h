@@ -490,6 +490,37 @@ int kh_tri_solve(kh_ctx ctx, kh_tri t, kh_vec X, int64_t xcol, kh_vec Y, int64_t
  * longest row. */
 int kh_tri_info(kh_tri t, int64_t out[8]);
 
+/* ---- ILU(0) factorisation and the multicolour ordering ------------------------------------------------------------------- */
+/* All three entry points serve the M, Ml, Mr hooks of krypy/linsys.py: they build, from A alone, the factors kh_tri_create
+ * takes.  No reference counterpart - the reference calls the user's function on host arrays.  ILU(0) keeps the pattern of A
+ * (krypy_amd/csrc/ilu0.h, ilu0.hip), in place on a copy a of the values, one thread per row, rows scheduled by the levels of
+ * tril(A, -1):  for the entries p of row i with k = col[p] < i, ascending:  a[p] = a[p] / a[diagonal of row k];  for the entries
+ * q of row i behind p whose column row k also holds (entry r):  a[q] = a[q] - a[p] * a[r]  (multiply and subtract rounded
+ * separately) - the bits of the sequential row-by-row loop. */
+/* M / Ml / Mr hooks, no reference counterpart.  A as CSR with SORTED, duplicate-free int32 indices and a structural diagonal
+ * entry in every row (stored zeros belong to the pattern).  Uploads pattern, values and plan, factors on the device, downloads
+ * the factored values into lu_out (the CSR positions of data: L strictly below the diagonal, its unit diagonal implied; U on and
+ * above it) and frees everything.  info = n, nnz, levels, wide launches, narrow launches, rows of the widest level, entries of
+ * the longest row, first row that broke down or -1.  A breakdown (a finished pivot that is zero or not finite) is NOT an error:
+ * the call returns 0, info[7] is the smallest such row and lu_out holds what the sequential loop holds when it goes on.
+ * kh_ctx_set "tri_narrow_rows" decides the two kinds of launch as for kh_tri_create.  KH_ERR_ARG (the row named): n or nnz out of
+ * int32 range, unsorted or duplicate indices, a column out of range, a row without a diagonal entry; KH_ERR_NOMEM: an allocation
+ * failed; KH_ERR_UNSUPPORTED: the context has a communicator (sharded factorisations do not exist).  Nothing stays allocated on
+ * any way out.  Counters (kh_ctx_get): "n_ilu0_factor" calls, "n_ilu0_wide" / "n_ilu0_narrow" launches of the two kinds,
+ * "ilu0_device_us" the device time of the last call's launches (HIP events around them). */
+int kh_ilu0_factor(kh_ctx ctx, int64_t n, int64_t nnz, const int32_t* indptr, const int32_t* indices, const double* data,
+                   double* lu_out, int64_t info[8]);
+/* M / Ml / Mr hooks with complex data, no reference counterpart: the same with (re, im) pairs; NumPy's complex product and
+ * quotient (Smith's formula), as kh_ztri_create.  A pivot is zero when both parts are. */
+int kh_zilu0_factor(kh_ctx ctx, int64_t n, int64_t nnz, const int32_t* indptr, const int32_t* indices, const double* data_re_im,
+                    double* lu_out_re_im, int64_t info[8]);
+/* M / Ml / Mr hooks, no reference counterpart (host only, no context): greedy colouring of the graph given as a CSR pattern - the
+ * caller passes the pattern of A + A^T, a diagonal entry is ignored.  Rows in ascending order, each takes the smallest colour
+ * that no already-coloured neighbour holds; color_out[i] in [0, *ncolors).  The multicolour ordering is the stable sort of the
+ * rows by colour: rows of one colour do not depend on each other, so ILU(0) of the reordered matrix has at most *ncolors levels
+ * per factor.  KH_ERR_ARG: n or nnz out of int32 range, a column out of range. */
+int kh_multicolor(int64_t n, int64_t nnz, const int32_t* indptr, const int32_t* indices, int32_t* color_out, int64_t* ncolors);
+
 /* ---- Chebyshev polynomial preconditioner -------------------------------------------------------------------------------- */
 /* Both entry points serve the M, Ml, Mr hooks of krypy/linsys.py: z = p(A) r as m steps of the Chebyshev iteration for A z = r
  * from z = 0, for a Hermitian positive definite A with spectrum in [lmin, lmax] (of Dinv A when scaled).  No reference

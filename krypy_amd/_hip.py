@@ -114,6 +114,10 @@ _SIGNATURES = {
     "kh_tri_free": [_H],
     "kh_tri_solve": [_H, _H, _H, _I64, _H, _I64, _I64],
     "kh_tri_info": [_H, _c_int64_p],
+    # ILU(0) factorisation and the multicolour ordering (csrc/ilu0.hip)
+    "kh_ilu0_factor": [_H, _I64, _I64, _c_int32_p, _c_int32_p, _c_double_p, _c_double_p, _c_int64_p],
+    "kh_zilu0_factor": [_H, _I64, _I64, _c_int32_p, _c_int32_p, _c_double_p, _c_double_p, _c_int64_p],
+    "kh_multicolor": [_I64, _I64, _c_int32_p, _c_int32_p, _c_int32_p, _c_int64_p],
     # Chebyshev polynomial preconditioner (csrc/cheb.hip)
     "kh_cheb_update": [_H, _H, _I64, _H, _I64, _H, _H, _I64, _H, _I64, _H, _I64, _D, _D, _INT],
     "kh_cheb_apply": [_H, _H, _H, _INT, _c_double_p, _H, _I64, _H, _I64, _I64, _H],
@@ -739,6 +743,26 @@ class Context(object):
         _check(self._lib, self._lib.kh_tri_solve(self._h, t.handle, X.handle, xcol, Y.handle, ycol, ncols),
                "kh_tri_solve")
 
+    def ilu0(self, A, dtype=None):
+        """ILU(0) of a square SciPy CSR matrix with sorted, duplicate-free indices and a structural diagonal, factored on the
+        device (``kh_ilu0_factor`` / ``kh_zilu0_factor``).  Returns ``(lu_data, info)``: the factored values at the CSR
+        positions of ``A.data`` (``L`` strictly below the diagonal, ``U`` on and above it) and the plan as a dict.  A
+        breakdown is not an error here: ``info["first_broken_row"]`` names the row (-1: none)."""
+        indptr = numpy.ascontiguousarray(A.indptr, dtype=numpy.int32)
+        indices = numpy.ascontiguousarray(A.indices, dtype=numpy.int32)
+        dt = _block_dtype(A.dtype if dtype is None else numpy.result_type(A.dtype, dtype))
+        data = numpy.ascontiguousarray(A.data, dtype=dt)
+        if A.shape[0] != A.shape[1]:
+            raise BackendError("ilu0: a square matrix expected, got %s" % (A.shape,))
+        lu = numpy.empty_like(data)
+        buf = (ctypes.c_int64 * 8)()
+        fn = self._lib.kh_zilu0_factor if dt == _C128 else self._lib.kh_ilu0_factor
+        _check(self._lib, self._with_memory(lambda: fn(
+            self._h, A.shape[0], data.size, indptr.ctypes.data_as(_c_int32_p), indices.ctypes.data_as(_c_int32_p),
+            _dptr(data), _dptr(lu), buf)), "kh_ilu0_factor")
+        return lu, dict(n=buf[0], nnz=buf[1], levels=buf[2], wide_launches=buf[3], narrow_launches=buf[4],
+                        widest_level=buf[5], longest_row=buf[6], first_broken_row=buf[7])
+
     def cheb_update(self, AZ, azcol, R, rcol, Dinv, D, dcol, Zin, zincol, Zout, zoutcol, a, b, first=False):
         """One composed step of the Chebyshev iteration on single columns (``kh_cheb_update``): ``first`` is step 0
         (``AZ`` / ``Zin`` may be None), otherwise ``AZ[:, azcol]`` holds ``A z_in``.  ``Dinv``: a real diagonal
@@ -1148,6 +1172,21 @@ def device_count():
     n = _INT(0)
     rc = lib.kh_device_count(ctypes.byref(n))
     return int(n.value) if rc == 0 else 0
+
+
+def multicolor(G):
+    """Greedy colouring of the graph given as a SciPy CSR pattern (``kh_multicolor``; host code of the library, no device
+    and no context): rows in ascending order, each takes the smallest colour no already-coloured neighbour holds.  Pass
+    the pattern of ``A + A^T``.  Returns ``(color, ncolors)``, ``color`` an int32 array."""
+    lib = load_library()
+    indptr = numpy.ascontiguousarray(G.indptr, dtype=numpy.int32)
+    indices = numpy.ascontiguousarray(G.indices, dtype=numpy.int32)
+    color = numpy.zeros(G.shape[0], dtype=numpy.int32)
+    nc = _I64(0)
+    _check(lib, lib.kh_multicolor(G.shape[0], indices.size, indptr.ctypes.data_as(_c_int32_p),
+                                  indices.ctypes.data_as(_c_int32_p), color.ctypes.data_as(_c_int32_p), ctypes.byref(nc)),
+           "kh_multicolor")
+    return color, int(nc.value)
 
 
 def get_context():

@@ -31,7 +31,7 @@ __all__ = [
     "ZeroLinearOperator", "Projection", "arnoldi", "arnoldi_res", "find_common_dtype",
     "get_linearoperator", "inner", "ip_euclid", "norm", "norm_squared", "orthonormality", "qr",
     "shape_vec", "shape_vecs", "DVec", "Timer", "Timings", "TimedLinearOperator", "ritz",
-    "hegedus", "angles", "TriangularSolveOperator", "ilu_operator", "ChebyshevOperator", "chebyshev_operator",
+    "hegedus", "angles", "TriangularSolveOperator", "ilu_operator", "ilu0", "ilu0_operator", "ChebyshevOperator", "chebyshev_operator",
 ]
 
 
@@ -1010,6 +1010,118 @@ def ilu_operator(ilu):
     if not numpy.array_equal(perm_c, ar):
         op = MatrixLinearOperator(scipy.sparse.csr_matrix((numpy.ones(n), (ar, perm_c)), shape=(n, n))) * op
     return op
+
+
+class Ilu0Factors(object):
+    """What :func:`ilu0` returns: the attributes of ``scipy.sparse.linalg.spilu``'s result that :func:`ilu_operator` reads
+    (``L`` unit lower with explicit ones, ``U``, ``perm_r``, ``perm_c``, ``shape``, ``nnz``) plus ``info`` and ``solve``."""
+
+    def __init__(self, L, U, perm, info):
+        self.L, self.U, self.info = L, U, info
+        self.shape = L.shape
+        self.nnz = L.nnz + U.nnz
+        # solve: x[perm] = U^{-1} L^{-1} b[perm].  ilu_operator computes y[perm_r] = b; z = U^{-1} L^{-1} y; x = z[perm_c]:
+        # y = b[perm] and x[perm] = z hold for perm_r = perm_c = the inverse permutation
+        inv = numpy.empty_like(perm)
+        inv[perm] = numpy.arange(perm.size, dtype=perm.dtype)
+        self.perm, self.perm_r, self.perm_c = perm, inv, inv.copy()
+        self._op = None
+
+    @property
+    def operator(self):
+        """The solve as a device operator (:func:`ilu_operator` of this object), built once."""
+        if self._op is None:
+            self._op = ilu_operator(self)
+        return self._op
+
+    def solve(self, b):
+        """``x`` with ``x[p] = U^{-1} L^{-1} b[p]`` for one vector or the columns of an ``(n, k)`` array, through the device
+        operator."""
+        b = numpy.asarray(b)
+        x = self.operator.dot(b.reshape(self.shape[0], -1))
+        return x.reshape(b.shape) if b.ndim == 1 else x
+
+
+def ilu0(A, ordering="natural"):
+    """ILU(0) of ``A`` - the incomplete LU factorisation on the pattern of ``A`` itself, no pivoting, no fill - computed on the
+    device (``Context.ilu0``): an object that quacks like ``scipy.sparse.linalg.spilu``'s result, so :func:`ilu_operator`
+    takes it unchanged.  The reference has no counterpart (it takes any callable as a preconditioner).
+
+    ``A``: a SciPy sparse matrix, a dense array or a :class:`MatrixLinearOperator`, square, with a structural diagonal entry
+    in every row; stored zeros stay in the pattern.  ``ordering="natural"`` factors ``A`` as it is; ``"multicolor"`` factors
+    ``A[p][:, p]`` for the permutation ``p`` that sorts the rows by the colours of a greedy colouring of ``A + A^T`` - rows
+    of one colour do not depend on each other, so each factor has as many levels as there are colours (2 for a 5-point
+    stencil) where the natural order has as many as the grid has anti-diagonals.  The multicolour factors precondition
+    worse: which ordering solves faster is a matter of measurement.  ``solve(b)`` computes ``x[p] = U^{-1} L^{-1} b[p]``.
+
+    Solver hooks: ``Ml`` / ``Mr`` of GMRES for a nonsymmetric ``A``; ``M`` of CG / MINRES for a symmetric ``A``, where
+    ILU(0) is ``L D L^T`` and ``M`` is symmetric up to rounding.  Look at ``info["levels"]`` (and, once applied, at the
+    ``levels`` of the two triangular operators' ``info()``) before trusting the speed: the factorisation takes one
+    launch step per level, and so does every triangular solve.
+
+    ``info``: ``n, nnz, levels, wide_launches, narrow_launches, widest_level, longest_row, first_broken_row`` of the
+    factorisation's plan, ``ordering`` and ``colors`` (None for the natural order).  Raises :class:`ArgumentError` for a
+    matrix that is not square, a missing diagonal entry, an unknown ordering and a breakdown (a pivot that is zero or
+    not finite)."""
+    if ordering not in ("natural", "multicolor"):
+        raise ArgumentError("ordering %r: 'natural' or 'multicolor' expected" % (ordering,))
+    if isinstance(A, MatrixLinearOperator):
+        A = A._A
+        if A is None:
+            raise ArgumentError("ilu0 needs the matrix: this operator exists on the device only")
+    if not _is_sparse(A):
+        A = numpy.asarray(A)
+        if A.ndim != 2:
+            raise ArgumentError("a matrix expected, got an array of shape %s" % (A.shape,))
+    A = scipy.sparse.csr_matrix(A, copy=True)
+    if A.shape[0] != A.shape[1]:
+        raise ArgumentError("a square matrix expected, got shape %s" % (A.shape,))
+    A.sum_duplicates()
+    A.sort_indices()
+    if A.dtype not in (numpy.dtype(numpy.float64), numpy.dtype(numpy.complex128)):
+        A = A.astype(_bdt(A.dtype))
+    n = A.shape[0]
+    rows = numpy.repeat(numpy.arange(n), numpy.diff(A.indptr))
+    has_diag = numpy.zeros(n, dtype=bool)
+    has_diag[rows[A.indices == rows]] = True
+    if not has_diag.all():
+        raise ArgumentError("A has no diagonal entry in row %d: ILU(0) needs a structural diagonal" % int(numpy.flatnonzero(~has_diag)[0]))
+    perm, ncolors = numpy.arange(n), None
+    if ordering == "multicolor":
+        G = scipy.sparse.csr_matrix((numpy.ones(A.nnz), A.indices, A.indptr), shape=A.shape)
+        G = (G + G.T).tocsr()
+        G.sort_indices()
+        color, ncolors = _hip.multicolor(G)
+        perm = numpy.argsort(color, kind="stable")
+        inv = numpy.empty_like(perm)
+        inv[perm] = numpy.arange(n)
+        # A[perm][:, perm] with stored zeros kept: rows gathered, columns renamed, indices sorted again
+        cnt = numpy.diff(A.indptr)[perm]
+        indptr = numpy.concatenate([[0], numpy.cumsum(cnt)])
+        take = numpy.repeat(A.indptr[:-1][perm] - indptr[:-1], cnt) + numpy.arange(A.nnz)
+        A = scipy.sparse.csr_matrix((A.data[take], inv[A.indices[take]], indptr), shape=A.shape)
+        A.sort_indices()
+        rows = numpy.repeat(numpy.arange(n), cnt)
+    lu, info = _hip.get_context().ilu0(A)
+    bad = info["first_broken_row"]
+    if bad >= 0:
+        raise ArgumentError("ILU(0) breaks down: zero or non-finite pivot in row %d" % bad
+                            + (" (row %d of the original numbering)" % int(perm[bad]) if ordering == "multicolor" else ""))
+    low, up = A.indices <= rows, A.indices >= rows
+    ldata = numpy.where(A.indices == rows, numpy.ones(1, dtype=lu.dtype), lu)[low]
+    factors = []
+    for mask, data in ((low, ldata), (up, lu[up])):
+        ptr = numpy.concatenate([[0], numpy.cumsum(numpy.bincount(rows[mask], minlength=n))])
+        factors.append(scipy.sparse.csr_matrix((data, A.indices[mask], ptr), shape=A.shape))
+    return Ilu0Factors(factors[0], factors[1], perm, dict(info, ordering=ordering, colors=ncolors))
+
+
+def ilu0_operator(A, ordering="natural"):
+    """``ilu_operator(ilu0(A, ordering))``: the ILU(0) preconditioner of ``A`` as a device operator - factored on the device,
+    applied by two level-scheduled triangular solves.  ``Ml`` / ``Mr`` of GMRES for a nonsymmetric ``A``, ``M`` of CG /
+    MINRES for a symmetric one (ILU(0) is then ``L D L^T``, symmetric up to rounding); see :func:`ilu0` for the orderings
+    and for ``info["levels"]``, the number to look at before trusting the speed."""
+    return ilu_operator(ilu0(A, ordering))
 
 
 def chebyshev_coefficients(lmin, lmax, degree):
