@@ -521,6 +521,28 @@ int kh_zilu0_factor(kh_ctx ctx, int64_t n, int64_t nnz, const int32_t* indptr, c
  * per factor.  KH_ERR_ARG: n or nnz out of int32 range, a column out of range. */
 int kh_multicolor(int64_t n, int64_t nnz, const int32_t* indptr, const int32_t* indices, int32_t* color_out, int64_t* ncolors);
 
+/* ---- Sparse approximate inverse on a fixed pattern ------------------------------------------------------------------------ */
+/* M / Ml / Mr hooks, no reference counterpart: the preconditioner as a MATRIX, which kh_apply and the fused Arnoldi step take
+ * like any other.  Row i of M minimises || e_i^T - m^T A[J, :] ||_2 over the values m at the pattern columns J of row i (at most 32;
+ * so M minimises || I - M A ||_F on the pattern): normal equations by a root-free Cholesky factorisation, every multiply, add and
+ * divide rounded on its own - the contract is in krypy_amd/csrc/spai.h, the result does not depend on how the device splits a row.
+ * A (n, nnz, indptr, indices, data) and the pattern (pnnz, pindptr, pindices; n rows) as CSR with SORTED, duplicate-free int32
+ * indices.  Uploads, launches ONCE (one group of lanes per row, the small matrices in LDS), downloads the values into m_out (the
+ * CSR positions of the pattern; a row without pattern entries writes nothing) and frees everything.  info = n, pnnz, entries of
+ * the longest pattern row, lanes per row, workgroups, LDS bytes per workgroup, reserved (0), first row that broke down or -1.
+ * A breakdown (the rows of A a pattern row selects are linearly dependent: a pivot d_j that is not > 0 or not finite) is NOT an
+ * error: the call returns 0, info[7] is the smallest such row and m_out holds what IEEE arithmetic makes of it.  KH_ERR_ARG (the
+ * row named): n, nnz or pnnz out of int32 range, unsorted or duplicate indices in A or in the pattern, a column out of range, a
+ * pattern row with more than 32 entries; KH_ERR_NOMEM: an allocation failed; KH_ERR_UNSUPPORTED: the context has a communicator
+ * (sharded construction does not exist).  Nothing stays allocated on any way out.  Counters (kh_ctx_get): "n_spai_build" calls,
+ * "spai_device_us" the device time of the last call's launch (HIP events around it). */
+int kh_spai_build(kh_ctx ctx, int64_t n, int64_t nnz, const int32_t* indptr, const int32_t* indices, const double* data, int64_t pnnz,
+                  const int32_t* pindptr, const int32_t* pindices, double* m_out, int64_t info[8]);
+/* M / Ml / Mr hooks with complex data, no reference counterpart: the same with (re, im) pairs; G = conj(A[J, :]) A[J, :]^T is
+ * Hermitian, the product is (ac - bd, ad + bc), a complex value times or over a real pivot is taken part by part. */
+int kh_zspai_build(kh_ctx ctx, int64_t n, int64_t nnz, const int32_t* indptr, const int32_t* indices, const double* data_re_im,
+                   int64_t pnnz, const int32_t* pindptr, const int32_t* pindices, double* m_out_re_im, int64_t info[8]);
+
 /* ---- Chebyshev polynomial preconditioner -------------------------------------------------------------------------------- */
 /* Both entry points serve the M, Ml, Mr hooks of krypy/linsys.py: z = p(A) r as m steps of the Chebyshev iteration for A z = r
  * from z = 0, for a Hermitian positive definite A with spectrum in [lmin, lmax] (of Dinv A when scaled).  No reference

@@ -118,6 +118,9 @@ _SIGNATURES = {
     "kh_ilu0_factor": [_H, _I64, _I64, _c_int32_p, _c_int32_p, _c_double_p, _c_double_p, _c_int64_p],
     "kh_zilu0_factor": [_H, _I64, _I64, _c_int32_p, _c_int32_p, _c_double_p, _c_double_p, _c_int64_p],
     "kh_multicolor": [_I64, _I64, _c_int32_p, _c_int32_p, _c_int32_p, _c_int64_p],
+    # sparse approximate inverse on a fixed pattern (csrc/spai.hip)
+    "kh_spai_build": [_H, _I64, _I64, _c_int32_p, _c_int32_p, _c_double_p, _I64, _c_int32_p, _c_int32_p, _c_double_p, _c_int64_p],
+    "kh_zspai_build": [_H, _I64, _I64, _c_int32_p, _c_int32_p, _c_double_p, _I64, _c_int32_p, _c_int32_p, _c_double_p, _c_int64_p],
     # Chebyshev polynomial preconditioner (csrc/cheb.hip)
     "kh_cheb_update": [_H, _H, _I64, _H, _I64, _H, _H, _I64, _H, _I64, _H, _I64, _D, _D, _INT],
     "kh_cheb_apply": [_H, _H, _H, _INT, _c_double_p, _H, _I64, _H, _I64, _I64, _H],
@@ -762,6 +765,30 @@ class Context(object):
             _dptr(data), _dptr(lu), buf)), "kh_ilu0_factor")
         return lu, dict(n=buf[0], nnz=buf[1], levels=buf[2], wide_launches=buf[3], narrow_launches=buf[4],
                         widest_level=buf[5], longest_row=buf[6], first_broken_row=buf[7])
+
+    def spai(self, A, P):
+        """The sparse approximate inverse of the square SciPy CSR matrix ``A`` on the pattern of the CSR matrix ``P`` (both with
+        sorted, duplicate-free indices, at most 32 entries per row of ``P``), built on the device in one launch
+        (``kh_spai_build`` / ``kh_zspai_build``): row ``i`` minimises ``|| e_i^T - m^T A[J_i, :] ||_2`` over the pattern columns
+        ``J_i``.  Returns ``(m_data, info)``: the values at the CSR positions of ``P`` and a dict.  A breakdown is not an error
+        here: ``info["first_broken_row"]`` names the row (-1: none)."""
+        if A.shape[0] != A.shape[1] or P.shape != A.shape:
+            raise BackendError("spai: a square matrix and a pattern of its shape expected, got %s and %s" % (A.shape, P.shape))
+        indptr = numpy.ascontiguousarray(A.indptr, dtype=numpy.int32)
+        indices = numpy.ascontiguousarray(A.indices, dtype=numpy.int32)
+        pindptr = numpy.ascontiguousarray(P.indptr, dtype=numpy.int32)
+        pindices = numpy.ascontiguousarray(P.indices, dtype=numpy.int32)
+        dt = _block_dtype(A.dtype)
+        data = numpy.ascontiguousarray(A.data, dtype=dt)
+        m = numpy.empty(pindices.size, dtype=dt)
+        buf = (ctypes.c_int64 * 8)()
+        fn = self._lib.kh_zspai_build if dt == _C128 else self._lib.kh_spai_build
+        _check(self._lib, self._with_memory(lambda: fn(
+            self._h, A.shape[0], data.size, indptr.ctypes.data_as(_c_int32_p), indices.ctypes.data_as(_c_int32_p), _dptr(data),
+            pindices.size, pindptr.ctypes.data_as(_c_int32_p), pindices.ctypes.data_as(_c_int32_p), _dptr(m), buf)),
+            "kh_spai_build")
+        return m, dict(n=buf[0], pnnz=buf[1], qmax=buf[2], group_width=buf[3], workgroups=buf[4], lds_bytes=buf[5],
+                       first_broken_row=buf[7])
 
     def cheb_update(self, AZ, azcol, R, rcol, Dinv, D, dcol, Zin, zincol, Zout, zoutcol, a, b, first=False):
         """One composed step of the Chebyshev iteration on single columns (``kh_cheb_update``): ``first`` is step 0

@@ -1087,6 +1087,8 @@ int kh_ctx_get(kh_ctx ctx, const char* key, int64_t* value) {
     else if (!strcmp(key, "n_ilu0_wide")) *value = ctx->n_ilu0_wide;
     else if (!strcmp(key, "n_ilu0_narrow")) *value = ctx->n_ilu0_narrow;
     else if (!strcmp(key, "ilu0_device_us")) *value = ctx->ilu0_device_us;
+    else if (!strcmp(key, "n_spai_build")) *value = ctx->n_spai_build;
+    else if (!strcmp(key, "spai_device_us")) *value = ctx->spai_device_us;
     else if (!strcmp(key, "cheb_fused")) *value = ctx->cheb_fused;
     else if (!strcmp(key, "n_cheb_apply")) *value = ctx->n_cheb_apply;
     else if (!strcmp(key, "n_cheb_fused")) *value = ctx->n_cheb_fused;

@@ -31,7 +31,7 @@ __all__ = [
     "ZeroLinearOperator", "Projection", "arnoldi", "arnoldi_res", "find_common_dtype",
     "get_linearoperator", "inner", "ip_euclid", "norm", "norm_squared", "orthonormality", "qr",
     "shape_vec", "shape_vecs", "DVec", "Timer", "Timings", "TimedLinearOperator", "ritz",
-    "hegedus", "angles", "TriangularSolveOperator", "ilu_operator", "ilu0", "ilu0_operator", "ChebyshevOperator", "chebyshev_operator",
+    "hegedus", "angles", "TriangularSolveOperator", "ilu_operator", "ilu0", "ilu0_operator", "spai", "spai_operator", "ChebyshevOperator", "chebyshev_operator",
 ]
 
 
@@ -1122,6 +1122,99 @@ def ilu0_operator(A, ordering="natural"):
     MINRES for a symmetric one (ILU(0) is then ``L D L^T``, symmetric up to rounding); see :func:`ilu0` for the orderings
     and for ``info["levels"]``, the number to look at before trusting the speed."""
     return ilu_operator(ilu0(A, ordering))
+
+
+_SPAI_MAX_ROW = 32
+
+
+def _spai_matrix(A, what):
+    """A square canonical CSR copy (duplicates summed, indices sorted, stored zeros kept) of a sparse matrix, a dense array or a
+    MatrixLinearOperator that has a host matrix."""
+    if isinstance(A, MatrixLinearOperator):
+        A = A._A
+        if A is None:
+            raise ArgumentError("spai needs the matrix: this operator exists on the device only")
+    if not _is_sparse(A):
+        A = numpy.asarray(A)
+        if A.ndim != 2:
+            raise ArgumentError("%s: a matrix expected, got an array of shape %s" % (what, A.shape,))
+    A = scipy.sparse.csr_matrix(A, copy=True)
+    A.sum_duplicates()
+    A.sort_indices()
+    return A
+
+
+def spai(A, pattern=None, side="left", symmetric=False):
+    """The sparse approximate inverse of ``A`` on a fixed pattern (static-pattern SPAI), built on the device in one launch
+    (``Context.spai``): a ``scipy.sparse.csr_matrix`` ``M`` with ``M.info`` (a dict).  A preconditioner given as a matrix: as
+    ``Ml`` / ``Mr`` it is one sparse product per step, as ``M`` the fused Arnoldi step applies it itself.  The reference has no
+    counterpart (it takes any callable as a preconditioner).
+
+    ``side="left"`` minimises ``|| I - M A ||_F`` over all ``M`` with the given pattern (for ``Ml``), ``side="right"``
+    ``|| I - A M ||_F`` (for ``Mr``; computed as ``spai(A.T, pattern.T, "left").T``, plain transposes on the host).  Every row is
+    a small least-squares problem of its own, solved through its normal equations.  ``A``: a SciPy sparse matrix, a dense array
+    or a :class:`MatrixLinearOperator`, square; float32 / complex64 are widened.  ``pattern=None`` is the pattern of ``A``
+    (stored zeros kept); otherwise any sparse or dense matrix of ``A``'s shape of which only the pattern is read, ``A @ A`` for
+    example; at most 32 entries per row (per column for ``side="right"``).
+
+    ``symmetric=True`` returns ``(M + M^H) / 2``, formed on the host - for the ``M`` hook of CG and MINRES with a Hermitian
+    ``A``.  Positive definiteness of the result is NOT checked.
+
+    ``info``: ``n, pnnz, qmax, group_width, workgroups, lds_bytes, first_broken_row`` of the device call, ``side`` and
+    ``symmetric``.  Raises :class:`ArgumentError` for a matrix that is not square, a pattern of another shape, an unknown
+    side, a pattern row with more than 32 entries and a breakdown (the rows of ``A`` a pattern row selects are linearly
+    dependent)."""
+    if side not in ("left", "right"):
+        raise ArgumentError("side %r: 'left' or 'right' expected" % (side,))
+    A = _spai_matrix(A, "A")
+    if A.shape[0] != A.shape[1]:
+        raise ArgumentError("a square matrix expected, got shape %s" % (A.shape,))
+    if A.dtype not in (numpy.dtype(numpy.float64), numpy.dtype(numpy.complex128)):
+        A = A.astype(_bdt(A.dtype))
+    if pattern is None:
+        P = A
+    else:
+        if isinstance(pattern, MatrixLinearOperator) or _is_sparse(pattern):
+            P = _spai_matrix(pattern, "pattern")
+        else:
+            pattern = numpy.asarray(pattern)
+            if pattern.ndim != 2:
+                raise ArgumentError("pattern: a matrix expected, got an array of shape %s" % (pattern.shape,))
+            P = _spai_matrix(pattern != 0, "pattern")
+        if P.shape != A.shape:
+            raise ArgumentError("a pattern of shape %s expected, got %s" % (A.shape, P.shape))
+    if side == "right":
+        A = A.T.tocsr()
+        A.sort_indices()
+        if pattern is None:
+            P = A
+        else:
+            P = P.T.tocsr()
+            P.sort_indices()
+    long_rows = numpy.flatnonzero(numpy.diff(P.indptr) > _SPAI_MAX_ROW)
+    if long_rows.size:
+        i = int(long_rows[0])
+        raise ArgumentError("pattern %s %d has %d entries, at most %d are supported"
+                            % ("row" if side == "left" else "column", i, int(P.indptr[i + 1] - P.indptr[i]), _SPAI_MAX_ROW))
+    data, info = _hip.get_context().spai(A, P)
+    bad = info["first_broken_row"]
+    if bad >= 0:
+        raise ArgumentError("SPAI breaks down: rows of A selected by pattern row %d are linearly dependent" % bad)
+    M = scipy.sparse.csr_matrix((data, P.indices.copy(), P.indptr.copy()), shape=A.shape)
+    if side == "right":
+        M = M.T.tocsr()
+        M.sort_indices()
+    if symmetric:
+        M = ((M + M.conj().T) / 2).tocsr()
+        M.sort_indices()
+    M.info = dict(info, side=side, symmetric=bool(symmetric))
+    return M
+
+
+def spai_operator(A, **kw):
+    """``MatrixLinearOperator(spai(A, **kw))``: the sparse approximate inverse of ``A`` as a device operator - ``Ml`` / ``Mr``
+    of GMRES, or, with ``symmetric=True``, ``M`` of CG / MINRES (positive definiteness is not checked); see :func:`spai`."""
+    return MatrixLinearOperator(spai(A, **kw))
 
 
 def chebyshev_coefficients(lmin, lmax, degree):
