@@ -39,6 +39,7 @@ typedef struct kh_mat_s* kh_mat;
 typedef struct kh_vec_s* kh_vec;
 typedef struct kh_proj_s* kh_proj;
 typedef struct kh_tri_s* kh_tri;
+typedef struct kh_ilu0_s* kh_ilu0;
 
 typedef enum {
     KH_OK = 0,
@@ -520,6 +521,53 @@ int kh_zilu0_factor(kh_ctx ctx, int64_t n, int64_t nnz, const int32_t* indptr, c
  * rows by colour: rows of one colour do not depend on each other, so ILU(0) of the reordered matrix has at most *ncolors levels
  * per factor.  KH_ERR_ARG: n or nnz out of int32 range, a column out of range. */
 int kh_multicolor(int64_t n, int64_t nnz, const int32_t* indptr, const int32_t* indices, int32_t* color_out, int64_t* ncolors);
+
+/* ---- Persistent ILU(0) preconditioner: refactor and solve on the device ----------------------------------------------------- */
+/* All six entry points serve the M, Ml, Mr hooks of krypy/linsys.py over a SEQUENCE of systems with one pattern (time steps,
+ * Newton iterations): the analysis runs once, new values of A cost one upload and a few launches, the factors stay on the
+ * device and the ordering is folded into the solves.  No reference counterpart - the reference calls the user's function on
+ * host arrays.  With Ap = A[perm][:, perm] (perm NULL: Ap = A) the handle holds the ILU(0) factors L (unit lower) and U of Ap,
+ * the bits of kh_ilu0_factor on Ap, as the two sliced-ELL images kh_tri_create would build for them (krypy_amd/csrc/ilu0p.h,
+ * ilu0p.hip).  A handle type of its own: a kh_ilu0 is not a kh_mat and kh_apply never sees one. */
+/* M / Ml / Mr hooks, no reference counterpart.  The PATTERN of A as CSR with SORTED, duplicate-free int32 indices and a structural
+ * diagonal entry in every row; perm: new row r = old row perm[r], or NULL for the natural order; cplx != 0: values and blocks are
+ * (re, im) pairs.  Everything that does not depend on values runs here, once, on the host: the pattern of Ap and the position
+ * src[q] in the caller's value array of its entry q, the factorisation's plan (that of kh_ilu0_factor on Ap), the plans of L and
+ * U (those of kh_tri_create) and the maps from Ap's value array into the two images.  kh_ctx_set "tri_narrow_rows" is read
+ * HERE.  KH_ERR_ARG (the row named, in the caller's numbering): n or nnz out of int32 range, unsorted or duplicate indices, a
+ * column out of range, a row without a diagonal entry, perm not a permutation of 0 .. n-1; KH_ERR_NOMEM: an allocation failed
+ * (nothing half-built stays behind); KH_ERR_UNSUPPORTED: the context has a communicator.  Counter: "n_ilu0p_create". */
+int kh_ilu0_create(kh_ctx ctx, int64_t n, int64_t nnz, const int32_t* indptr, const int32_t* indices, const int32_t* perm, int cplx,
+                   kh_ilu0* out);
+/* M / Ml / Mr hooks, no reference counterpart.  Factors the values data (the caller's CSR positions; (re, im) pairs for a complex
+ * handle): ONE host-to-device copy of nnz values, then on the context's stream a gather a[q] = data[src[q]], the launches of
+ * kh_ilu0_factor's contract on Ap (arithmetic and plan), and one kernel that writes the off-diagonal slots of both images and U's
+ * diagonal through the maps.  The 4 bytes of the breakdown word are the only traffic back; no host analysis, no allocation, no
+ * sort.  info as kh_ilu0_factor's: n, nnz, levels, wide launches, narrow launches, rows of the widest level, entries of the
+ * longest row, first row that broke down IN THE NUMBERING OF Ap or -1.  A breakdown is NOT an error of the call, but the handle
+ * is then not factored until a later refactorisation succeeds.  Counters (kh_ctx_get): "n_ilu0p_refactor" calls,
+ * "ilu0p_h2d_bytes" / "ilu0p_d2h_bytes" / "ilu0p_refactor_us" of the last call (HIP events around gather, factorisation and
+ * fill), "n_ilu0p_wide" / "n_ilu0p_narrow" launches of the two kinds (shared with kh_ilu0_solve). */
+int kh_ilu0_refactor(kh_ctx ctx, kh_ilu0 h, const double* data, int64_t info[8]);
+/* M / Ml / Mr hooks, no reference counterpart.  Y[perm[i], ycol + c] = (U^{-1} L^{-1} b')_i with b'_i = X[perm[i], xcol + c],
+ * c < ncols (one column after the other) - the permutation inside the triangular kernels, compiled out for perm == NULL.  Per
+ * row the arithmetic of kh_tri_solve, to the bit.  All launches of the L stage precede those of the U stage, so X and Y may be
+ * the same columns; ranges of one block that overlap without being identical are KH_ERR_ARG.  Rows [n, ld) of Y are not
+ * written.  KH_ERR_ARG: the handle is not factored (never refactored, or the last refactorisation broke down); another
+ * context's handle; the length of the blocks does not match (also: a real handle on complex blocks or the reverse).  Counters:
+ * "n_ilu0p_solve" columns, "n_ilu0p_wide" / "n_ilu0p_narrow" launches. */
+int kh_ilu0_solve(kh_ctx ctx, kh_ilu0 h, kh_vec X, int64_t xcol, kh_vec Y, int64_t ycol, int64_t ncols);
+/* M / Ml / Mr hooks, no reference counterpart (diagnostics and tests): downloads the factored values to the positions of the
+ * caller's value array, lu_out[src[q]] = a[q] - L strictly below the diagonal of Ap, U on and above it.  KH_ERR_ARG on a handle
+ * that is not factored. */
+int kh_ilu0_values(kh_ilu0 h, double* lu_out);
+/* M / Ml / Mr hooks, no reference counterpart (diagnostics of the plan): out = n, nnz, levels of the factorisation, wide launches
+ * per refactorisation, narrow launches per refactorisation, levels of L, levels of U, wide launches per solve, narrow launches
+ * per solve, stored slots of L including padding, stored slots of U, permuted (0 / 1), factored (0 / 1), device bytes held,
+ * 0, 0 (reserved). */
+int kh_ilu0_info(kh_ilu0 h, int64_t out[16]);
+/* M / Ml / Mr hooks, no reference counterpart: releases everything the handle holds on the device (waits for the stream first). */
+int kh_ilu0_free(kh_ilu0 h);
 
 /* ---- Sparse approximate inverse on a fixed pattern ------------------------------------------------------------------------ */
 /* M / Ml / Mr hooks, no reference counterpart: the preconditioner as a MATRIX, which kh_apply and the fused Arnoldi step take

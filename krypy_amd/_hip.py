@@ -118,6 +118,13 @@ _SIGNATURES = {
     "kh_ilu0_factor": [_H, _I64, _I64, _c_int32_p, _c_int32_p, _c_double_p, _c_double_p, _c_int64_p],
     "kh_zilu0_factor": [_H, _I64, _I64, _c_int32_p, _c_int32_p, _c_double_p, _c_double_p, _c_int64_p],
     "kh_multicolor": [_I64, _I64, _c_int32_p, _c_int32_p, _c_int32_p, _c_int64_p],
+    # persistent ILU(0) preconditioner: refactor and solve on the device (csrc/ilu0p.hip)
+    "kh_ilu0_create": [_H, _I64, _I64, _c_int32_p, _c_int32_p, _c_int32_p, _INT, ctypes.POINTER(_H)],
+    "kh_ilu0_refactor": [_H, _H, _c_double_p, _c_int64_p],
+    "kh_ilu0_solve": [_H, _H, _H, _I64, _H, _I64, _I64],
+    "kh_ilu0_values": [_H, _c_double_p],
+    "kh_ilu0_info": [_H, _c_int64_p],
+    "kh_ilu0_free": [_H],
     # sparse approximate inverse on a fixed pattern (csrc/spai.hip)
     "kh_spai_build": [_H, _I64, _I64, _c_int32_p, _c_int32_p, _c_double_p, _I64, _c_int32_p, _c_int32_p, _c_double_p, _c_int64_p],
     "kh_zspai_build": [_H, _I64, _I64, _c_int32_p, _c_int32_p, _c_double_p, _I64, _c_int32_p, _c_int32_p, _c_double_p, _c_int64_p],
@@ -317,6 +324,38 @@ class DeviceTriangular(object):
         try:
             if self.handle is not None and self.ctx._alive:
                 self.ctx._lib.kh_tri_free(self.handle)
+        except Exception:
+            pass
+        self.handle = None
+
+
+class DeviceIlu0(object):
+    """A persistent ILU(0) preconditioner on the device (``kh_ilu0``): analysed once for a pattern and an ordering, refactored
+    for new values by ``Context.ilu0_refactor``, applied by ``Context.ilu0_solve``."""
+
+    def __init__(self, ctx, handle, shape, nnz, dtype):
+        self.ctx, self.handle, self.shape, self.nnz = ctx, handle, shape, nnz
+        self.dtype = numpy.dtype(dtype)
+
+    def info(self):
+        """The plan and the state (``kh_ilu0_info``)."""
+        buf = (ctypes.c_int64 * 16)()
+        _check(self.ctx._lib, self.ctx._lib.kh_ilu0_info(self.handle, buf), "kh_ilu0_info")
+        return dict(n=buf[0], nnz=buf[1], levels=buf[2], wide_launches=buf[3], narrow_launches=buf[4], levels_l=buf[5],
+                    levels_u=buf[6], solve_wide_launches=buf[7], solve_narrow_launches=buf[8], slots_l=buf[9], slots_u=buf[10],
+                    permuted=bool(buf[11]), factored=bool(buf[12]), device_bytes=buf[13])
+
+    def values(self):
+        """The factored values at the positions of the caller's value array (``kh_ilu0_values``): ``L`` strictly below the
+        diagonal of the reordered matrix, ``U`` on and above it."""
+        lu = numpy.empty(self.nnz, dtype=self.dtype)
+        _check(self.ctx._lib, self.ctx._lib.kh_ilu0_values(self.handle, _dptr(lu)), "kh_ilu0_values")
+        return lu
+
+    def __del__(self):
+        try:
+            if self.handle is not None and self.ctx._alive:
+                self.ctx._lib.kh_ilu0_free(self.handle)
         except Exception:
             pass
         self.handle = None
@@ -765,6 +804,51 @@ class Context(object):
             _dptr(data), _dptr(lu), buf)), "kh_ilu0_factor")
         return lu, dict(n=buf[0], nnz=buf[1], levels=buf[2], wide_launches=buf[3], narrow_launches=buf[4],
                         widest_level=buf[5], longest_row=buf[6], first_broken_row=buf[7])
+
+    def ilu0_handle(self, A_pattern, perm=None, dtype=_F64):
+        """A persistent ILU(0) preconditioner for the PATTERN of the square SciPy CSR matrix ``A_pattern`` (sorted,
+        duplicate-free indices, a structural diagonal; its values are not looked at) under the ordering ``perm`` (new row
+        ``r`` = old row ``perm[r]``; None: the natural order) for values of ``dtype`` (``kh_ilu0_create``).  The whole
+        analysis runs here, once; the handle is not factored until :meth:`ilu0_refactor` succeeds."""
+        if A_pattern.shape[0] != A_pattern.shape[1]:
+            raise BackendError("ilu0_handle: a square matrix expected, got %s" % (A_pattern.shape,))
+        indptr = numpy.ascontiguousarray(A_pattern.indptr, dtype=numpy.int32)
+        indices = numpy.ascontiguousarray(A_pattern.indices, dtype=numpy.int32)
+        dt = _block_dtype(dtype)
+        pp = None
+        if perm is not None:
+            perm = numpy.ascontiguousarray(perm, dtype=numpy.int32)
+            if perm.shape != (A_pattern.shape[0],):
+                raise BackendError("ilu0_handle: perm of shape %s for %d rows" % (perm.shape, A_pattern.shape[0]))
+            pp = perm.ctypes.data_as(_c_int32_p)
+        h = _H()
+        _check(self._lib, self._with_memory(lambda: self._lib.kh_ilu0_create(
+            self._h, A_pattern.shape[0], indices.size, indptr.ctypes.data_as(_c_int32_p), indices.ctypes.data_as(_c_int32_p), pp,
+            1 if dt == _C128 else 0, ctypes.byref(h))), "kh_ilu0_create")
+        return DeviceIlu0(self, h, A_pattern.shape, indices.size, dt)
+
+    def ilu0_refactor(self, h, data):
+        """Factors the values ``data`` (at the CSR positions of the pattern the handle was made for) on the device
+        (``kh_ilu0_refactor``): one upload, no analysis.  Returns the ``info`` dict of :meth:`ilu0`; a breakdown is not an
+        error here - ``info["first_broken_row"]`` names the row of the reordered matrix (-1: none) - but leaves the handle
+        unusable until a later refactorisation succeeds."""
+        if numpy.asarray(data).dtype.kind == "c" and h.dtype != _C128:
+            raise BackendError("ilu0_refactor: complex values for a real handle")
+        data = numpy.ascontiguousarray(data, dtype=h.dtype)
+        if data.shape != (h.nnz,):
+            raise BackendError("ilu0_refactor: %s values for a pattern of %d entries" % (data.shape, h.nnz))
+        buf = (ctypes.c_int64 * 8)()
+        _check(self._lib, self._lib.kh_ilu0_refactor(self._h, h.handle, _dptr(data), buf), "kh_ilu0_refactor")
+        return dict(n=buf[0], nnz=buf[1], levels=buf[2], wide_launches=buf[3], narrow_launches=buf[4],
+                    widest_level=buf[5], longest_row=buf[6], first_broken_row=buf[7])
+
+    def ilu0_solve(self, h, X, xcol, Y, ycol, ncols=1):
+        """``Y[p, ycol:ycol+ncols] = U^{-1} L^{-1} X[p, xcol:xcol+ncols]`` with the handle's ordering ``p``
+        (``kh_ilu0_solve``); X and Y may be the same columns."""
+        if (h.dtype == _C128) != _same_dtype("ilu0_solve", X, Y):
+            raise BackendError("ilu0_solve: %s preconditioner on %s blocks" % (h.dtype, X.dtype))
+        _check(self._lib, self._lib.kh_ilu0_solve(self._h, h.handle, X.handle, xcol, Y.handle, ycol, ncols),
+               "kh_ilu0_solve")
 
     def spai(self, A, P):
         """The sparse approximate inverse of the square SciPy CSR matrix ``A`` on the pattern of the CSR matrix ``P`` (both with

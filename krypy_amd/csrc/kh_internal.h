@@ -102,6 +102,10 @@ struct kh_ctx_s {
     int64_t n_tri_solve = 0, n_tri_wide = 0, n_tri_narrow = 0;   // columns solved; launches of k_tri_wide / k_tri_narrow
     // ILU(0) factorisation (ilu0.hip): calls; launches of k_ilu0_wide / k_ilu0_narrow; device time of the last call's launches
     int64_t n_ilu0_factor = 0, n_ilu0_wide = 0, n_ilu0_narrow = 0, ilu0_device_us = 0;
+    // persistent ILU(0) preconditioner (ilu0p.hip): handles created; refactorisations; columns solved; launches of the wide / the
+    // one-workgroup kernels (factorisation and both solve stages); bytes up and down and device time of the last refactorisation
+    int64_t n_ilu0p_create = 0, n_ilu0p_refactor = 0, n_ilu0p_solve = 0, n_ilu0p_wide = 0, n_ilu0p_narrow = 0;
+    int64_t ilu0p_h2d_bytes = 0, ilu0p_d2h_bytes = 0, ilu0p_refactor_us = 0;
     // sparse approximate inverse (spai.hip): calls; device time of the last call's launch
     int64_t n_spai_build = 0, spai_device_us = 0;
     // Chebyshev polynomial preconditioner (cheb.hip): steps k >= 1 as ONE launch, the SpMV with the step in its epilogue

@@ -1087,6 +1087,14 @@ int kh_ctx_get(kh_ctx ctx, const char* key, int64_t* value) {
     else if (!strcmp(key, "n_ilu0_wide")) *value = ctx->n_ilu0_wide;
     else if (!strcmp(key, "n_ilu0_narrow")) *value = ctx->n_ilu0_narrow;
     else if (!strcmp(key, "ilu0_device_us")) *value = ctx->ilu0_device_us;
+    else if (!strcmp(key, "n_ilu0p_create")) *value = ctx->n_ilu0p_create;
+    else if (!strcmp(key, "n_ilu0p_refactor")) *value = ctx->n_ilu0p_refactor;
+    else if (!strcmp(key, "n_ilu0p_solve")) *value = ctx->n_ilu0p_solve;
+    else if (!strcmp(key, "n_ilu0p_wide")) *value = ctx->n_ilu0p_wide;
+    else if (!strcmp(key, "n_ilu0p_narrow")) *value = ctx->n_ilu0p_narrow;
+    else if (!strcmp(key, "ilu0p_h2d_bytes")) *value = ctx->ilu0p_h2d_bytes;
+    else if (!strcmp(key, "ilu0p_d2h_bytes")) *value = ctx->ilu0p_d2h_bytes;
+    else if (!strcmp(key, "ilu0p_refactor_us")) *value = ctx->ilu0p_refactor_us;
     else if (!strcmp(key, "n_spai_build")) *value = ctx->n_spai_build;
     else if (!strcmp(key, "spai_device_us")) *value = ctx->spai_device_us;
     else if (!strcmp(key, "cheb_fused")) *value = ctx->cheb_fused;

@@ -31,7 +31,7 @@ __all__ = [
     "ZeroLinearOperator", "Projection", "arnoldi", "arnoldi_res", "find_common_dtype",
     "get_linearoperator", "inner", "ip_euclid", "norm", "norm_squared", "orthonormality", "qr",
     "shape_vec", "shape_vecs", "DVec", "Timer", "Timings", "TimedLinearOperator", "ritz",
-    "hegedus", "angles", "TriangularSolveOperator", "ilu_operator", "ilu0", "ilu0_operator", "spai", "spai_operator", "ChebyshevOperator", "chebyshev_operator",
+    "hegedus", "angles", "TriangularSolveOperator", "ilu_operator", "ilu0", "ilu0_operator", "Ilu0Preconditioner", "ilu0_preconditioner", "spai", "spai_operator", "ChebyshevOperator", "chebyshev_operator",
 ]
 
 
@@ -1042,29 +1042,14 @@ class Ilu0Factors(object):
         return x.reshape(b.shape) if b.ndim == 1 else x
 
 
-def ilu0(A, ordering="natural"):
-    """ILU(0) of ``A`` - the incomplete LU factorisation on the pattern of ``A`` itself, no pivoting, no fill - computed on the
-    device (``Context.ilu0``): an object that quacks like ``scipy.sparse.linalg.spilu``'s result, so :func:`ilu_operator`
-    takes it unchanged.  The reference has no counterpart (it takes any callable as a preconditioner).
-
-    ``A``: a SciPy sparse matrix, a dense array or a :class:`MatrixLinearOperator`, square, with a structural diagonal entry
-    in every row; stored zeros stay in the pattern.  ``ordering="natural"`` factors ``A`` as it is; ``"multicolor"`` factors
-    ``A[p][:, p]`` for the permutation ``p`` that sorts the rows by the colours of a greedy colouring of ``A + A^T`` - rows
-    of one colour do not depend on each other, so each factor has as many levels as there are colours (2 for a 5-point
-    stencil) where the natural order has as many as the grid has anti-diagonals.  The multicolour factors precondition
-    worse: which ordering solves faster is a matter of measurement.  ``solve(b)`` computes ``x[p] = U^{-1} L^{-1} b[p]``.
-
-    Solver hooks: ``Ml`` / ``Mr`` of GMRES for a nonsymmetric ``A``; ``M`` of CG / MINRES for a symmetric ``A``, where
-    ILU(0) is ``L D L^T`` and ``M`` is symmetric up to rounding.  Look at ``info["levels"]`` (and, once applied, at the
-    ``levels`` of the two triangular operators' ``info()``) before trusting the speed: the factorisation takes one
-    launch step per level, and so does every triangular solve.
-
-    ``info``: ``n, nnz, levels, wide_launches, narrow_launches, widest_level, longest_row, first_broken_row`` of the
-    factorisation's plan, ``ordering`` and ``colors`` (None for the natural order).  Raises :class:`ArgumentError` for a
-    matrix that is not square, a missing diagonal entry, an unknown ordering and a breakdown (a pivot that is zero or
-    not finite)."""
+def _ilu0_check_ordering(ordering):
     if ordering not in ("natural", "multicolor"):
         raise ArgumentError("ordering %r: 'natural' or 'multicolor' expected" % (ordering,))
+
+
+def _ilu0_canonical(A):
+    """The matrix :func:`ilu0` and :class:`Ilu0Preconditioner` factor: a square fp64 / c128 CSR copy with duplicates summed,
+    indices sorted, stored zeros kept and a structural diagonal in every row."""
     if isinstance(A, MatrixLinearOperator):
         A = A._A
         if A is None:
@@ -1086,13 +1071,53 @@ def ilu0(A, ordering="natural"):
     has_diag[rows[A.indices == rows]] = True
     if not has_diag.all():
         raise ArgumentError("A has no diagonal entry in row %d: ILU(0) needs a structural diagonal" % int(numpy.flatnonzero(~has_diag)[0]))
-    perm, ncolors = numpy.arange(n), None
+    return A
+
+
+def _ilu0_ordering(A, ordering):
+    """``(perm, colors)`` of the canonical ``A``: the identity and None, or the rows sorted by the colours of the greedy
+    colouring of ``A + A^T`` and their number."""
+    if ordering != "multicolor":
+        return numpy.arange(A.shape[0]), None
+    G = scipy.sparse.csr_matrix((numpy.ones(A.nnz), A.indices, A.indptr), shape=A.shape)
+    G = (G + G.T).tocsr()
+    G.sort_indices()
+    color, ncolors = _hip.multicolor(G)
+    return numpy.argsort(color, kind="stable"), ncolors
+
+
+def _ilu0_breakdown(bad, perm, ordering):
+    return ArgumentError("ILU(0) breaks down: zero or non-finite pivot in row %d" % bad
+                         + (" (row %d of the original numbering)" % int(perm[bad]) if ordering == "multicolor" else ""))
+
+
+def ilu0(A, ordering="natural"):
+    """ILU(0) of ``A`` - the incomplete LU factorisation on the pattern of ``A`` itself, no pivoting, no fill - computed on the
+    device (``Context.ilu0``): an object that quacks like ``scipy.sparse.linalg.spilu``'s result, so :func:`ilu_operator`
+    takes it unchanged.  The reference has no counterpart (it takes any callable as a preconditioner).
+
+    ``A``: a SciPy sparse matrix, a dense array or a :class:`MatrixLinearOperator`, square, with a structural diagonal entry
+    in every row; stored zeros stay in the pattern.  ``ordering="natural"`` factors ``A`` as it is; ``"multicolor"`` factors
+    ``A[p][:, p]`` for the permutation ``p`` that sorts the rows by the colours of a greedy colouring of ``A + A^T`` - rows
+    of one colour do not depend on each other, so each factor has as many levels as there are colours (2 for a 5-point
+    stencil) where the natural order has as many as the grid has anti-diagonals.  The multicolour factors precondition
+    worse: which ordering solves faster is a matter of measurement.  ``solve(b)`` computes ``x[p] = U^{-1} L^{-1} b[p]``.
+
+    Solver hooks: ``Ml`` / ``Mr`` of GMRES for a nonsymmetric ``A``; ``M`` of CG / MINRES for a symmetric ``A``, where
+    ILU(0) is ``L D L^T`` and ``M`` is symmetric up to rounding.  Look at ``info["levels"]`` (and, once applied, at the
+    ``levels`` of the two triangular operators' ``info()``) before trusting the speed: the factorisation takes one
+    launch step per level, and so does every triangular solve.
+
+    ``info``: ``n, nnz, levels, wide_launches, narrow_launches, widest_level, longest_row, first_broken_row`` of the
+    factorisation's plan, ``ordering`` and ``colors`` (None for the natural order).  Raises :class:`ArgumentError` for a
+    matrix that is not square, a missing diagonal entry, an unknown ordering and a breakdown (a pivot that is zero or
+    not finite)."""
+    _ilu0_check_ordering(ordering)
+    A = _ilu0_canonical(A)
+    n = A.shape[0]
+    rows = numpy.repeat(numpy.arange(n), numpy.diff(A.indptr))
+    perm, ncolors = _ilu0_ordering(A, ordering)
     if ordering == "multicolor":
-        G = scipy.sparse.csr_matrix((numpy.ones(A.nnz), A.indices, A.indptr), shape=A.shape)
-        G = (G + G.T).tocsr()
-        G.sort_indices()
-        color, ncolors = _hip.multicolor(G)
-        perm = numpy.argsort(color, kind="stable")
         inv = numpy.empty_like(perm)
         inv[perm] = numpy.arange(n)
         # A[perm][:, perm] with stored zeros kept: rows gathered, columns renamed, indices sorted again
@@ -1103,10 +1128,8 @@ def ilu0(A, ordering="natural"):
         A.sort_indices()
         rows = numpy.repeat(numpy.arange(n), cnt)
     lu, info = _hip.get_context().ilu0(A)
-    bad = info["first_broken_row"]
-    if bad >= 0:
-        raise ArgumentError("ILU(0) breaks down: zero or non-finite pivot in row %d" % bad
-                            + (" (row %d of the original numbering)" % int(perm[bad]) if ordering == "multicolor" else ""))
+    if info["first_broken_row"] >= 0:
+        raise _ilu0_breakdown(info["first_broken_row"], perm, ordering)
     low, up = A.indices <= rows, A.indices >= rows
     ldata = numpy.where(A.indices == rows, numpy.ones(1, dtype=lu.dtype), lu)[low]
     factors = []
@@ -1122,6 +1145,119 @@ def ilu0_operator(A, ordering="natural"):
     MINRES for a symmetric one (ILU(0) is then ``L D L^T``, symmetric up to rounding); see :func:`ilu0` for the orderings
     and for ``info["levels"]``, the number to look at before trusting the speed."""
     return ilu_operator(ilu0(A, ordering))
+
+
+class Ilu0Preconditioner(LinearOperator):
+    """The ILU(0) preconditioner of ``A`` as ONE device operator that lives through a sequence of systems with the pattern of
+    ``A`` (time steps, Newton iterations, :class:`RecyclingGmres`): the analysis runs once (``Context.ilu0_handle``),
+    :meth:`update` factors new values with one upload and a few launches (``ilu0_refactor``), the factors never leave the
+    device, and an application is one ``ilu0_solve`` - ``x[p] = U^{-1} L^{-1} b[p]`` with the ordering ``p`` inside the two
+    triangular stages, no permutation products.  The reference has no counterpart (it takes any callable).
+
+    ``A`` and ``ordering`` as for :func:`ilu0`, which this object agrees with bit for bit (up to the sign of a zero the
+    permutation products of :func:`ilu_operator` lose).  ``Ml`` / ``Mr`` of GMRES, ``M`` of CG / MINRES for a symmetric
+    ``A``.  No adjoint.  ``_device_matrix()`` stays None: the solvers treat it as an external operator, applied once per
+    step.  A breakdown (a pivot that is zero or not finite) raises :class:`ArgumentError` from the constructor and from
+    :meth:`update`; after a failed update the object is unusable - applying it raises :class:`LinearOperatorError` - until an
+    update succeeds."""
+
+    def __init__(self, A, ordering="natural"):
+        _ilu0_check_ordering(ordering)
+        A = _ilu0_canonical(A)
+        super(Ilu0Preconditioner, self).__init__(A.shape, A.dtype, self._dot)
+        self._ordering = ordering
+        self._perm, self._colors = _ilu0_ordering(A, ordering)
+        self._pattern = scipy.sparse.csr_matrix((numpy.ones(A.nnz), A.indices, A.indptr), shape=A.shape)
+        self._data = A.data
+        self._handles = {}
+        self._broken = None
+        self._refactorisations = 0
+        self._device_handle(_hip.get_context(), self.dtype)      # a breakdown shows here, as in ilu0()
+
+    @property
+    def ordering(self):
+        return self._ordering
+
+    @property
+    def info(self):
+        """The plan of the device handle (``DeviceIlu0.info()``) plus ``ordering``, ``colors`` (None for the natural order)
+        and ``refactorisations``, the number of factorisations this object has run."""
+        h = self._handles.get((id(_hip.get_context()), self.dtype.kind)) or next(iter(self._handles.values()))
+        return dict(h.info(), ordering=self._ordering, colors=self._colors, refactorisations=self._refactorisations)
+
+    def _refactor(self, ctx, h):
+        info = ctx.ilu0_refactor(h, self._data)
+        self._refactorisations += 1
+        bad = info["first_broken_row"]
+        if bad >= 0:
+            self._broken = _ilu0_breakdown(bad, self._perm, self._ordering)
+            raise self._broken
+
+    def _device_handle(self, ctx, dtype=None):
+        """Device handle for blocks of ``dtype``: a real ``A`` gets a second, c128 handle when it meets complex vectors - factored
+        there in complex arithmetic, whose quotient rounds differently from the real one in the last bit."""
+        dt = _bdt(self.dtype, dtype)
+        key = (id(ctx), dt.kind)
+        h = self._handles.get(key)
+        if h is None:
+            h = ctx.ilu0_handle(self._pattern, None if self._ordering == "natural" else self._perm, dtype=dt)
+            self._refactor(ctx, h)
+            self._handles[key] = h
+        return h
+
+    def update(self, A_new):
+        """New values on the pattern this object was built with: canonicalised as in the constructor, then every existing
+        device handle is refactored.  Raises :class:`ArgumentError` for another pattern (the first differing row named),
+        another kind of values (real / complex) and a breakdown."""
+        A = _ilu0_canonical(A_new)
+        P = self._pattern
+        if A.shape != P.shape:
+            raise ArgumentError("update: a matrix of shape %s expected, got %s" % (P.shape, A.shape))
+        if A.dtype != self.dtype:
+            raise ArgumentError("update: %s values for a preconditioner built with %s" % (A.dtype, self.dtype))
+        if not (numpy.array_equal(A.indptr, P.indptr) and numpy.array_equal(A.indices, P.indices)):
+            n = P.shape[0]
+            ptr = numpy.flatnonzero(A.indptr != P.indptr)
+            r1 = int(ptr[0]) - 1 if ptr.size else n
+            m = int(P.indptr[r1]) if r1 < n else P.nnz          # the rows before r1 start at the same positions
+            idx = numpy.flatnonzero(A.indices[:m] != P.indices[:m])
+            r2 = int(numpy.searchsorted(P.indptr, idx[0], side="right")) - 1 if idx.size else n
+            raise ArgumentError("update: the pattern differs from the one the preconditioner was built with, first in row %d"
+                                % min(r1, r2))
+        self._data = A.data
+        self._broken = None
+        for h in list(self._handles.values()):
+            self._refactor(h.ctx, h)
+
+    def _usable(self):
+        if self._broken is not None:
+            raise LinearOperatorError("the last refactorisation broke down (%s): update() with a matrix that factors first"
+                                      % self._broken)
+
+    def _apply_dev(self, X, xcol, Y, ycol, ncols=1):
+        self._usable()
+        if _is_c(self.dtype) and not _is_c(X.dtype):
+            raise LinearOperatorError("complex ILU(0) preconditioner applied to a real device block")
+        X.ctx.ilu0_solve(self._device_handle(X.ctx, X.dtype), X, xcol, Y, ycol, ncols)
+
+    def _dot(self, X):
+        self._usable()
+        X = numpy.asarray(X)
+        ctx = _hip.get_context()
+        dt = _bdt(self.dtype, X.dtype)
+        Xd = ctx.upload(X, dtype=dt)
+        Yd = ctx.alloc(self.shape[0], X.shape[1], dtype=dt)
+        self._apply_dev(Xd, 0, Yd, 0, X.shape[1])
+        return numpy.ascontiguousarray(Yd.download())
+
+    def __repr__(self):
+        return "<%dx%d Ilu0Preconditioner (%s) with dtype=%s>" % (self.shape[0], self.shape[1], self._ordering, self.dtype)
+
+
+def ilu0_preconditioner(A, ordering="natural"):
+    """``Ilu0Preconditioner(A, ordering)``: the persistent ILU(0) preconditioner - see the class; call ``update(A_new)`` on it
+    when the values of ``A`` change and its pattern does not."""
+    return Ilu0Preconditioner(A, ordering)
 
 
 _SPAI_MAX_ROW = 32
