@@ -128,6 +128,9 @@ _SIGNATURES = {
     # sparse approximate inverse on a fixed pattern (csrc/spai.hip)
     "kh_spai_build": [_H, _I64, _I64, _c_int32_p, _c_int32_p, _c_double_p, _I64, _c_int32_p, _c_int32_p, _c_double_p, _c_int64_p],
     "kh_zspai_build": [_H, _I64, _I64, _c_int32_p, _c_int32_p, _c_double_p, _I64, _c_int32_p, _c_int32_p, _c_double_p, _c_int64_p],
+    # factorized sparse approximate inverse on a fixed lower-triangular pattern (csrc/fsai.hip)
+    "kh_fsai_build": [_H, _I64, _I64, _c_int32_p, _c_int32_p, _c_double_p, _I64, _c_int32_p, _c_int32_p, _c_double_p, _c_double_p, _c_int64_p],
+    "kh_zfsai_build": [_H, _I64, _I64, _c_int32_p, _c_int32_p, _c_double_p, _I64, _c_int32_p, _c_int32_p, _c_double_p, _c_double_p, _c_int64_p],
     # Chebyshev polynomial preconditioner (csrc/cheb.hip)
     "kh_cheb_update": [_H, _H, _I64, _H, _I64, _H, _H, _I64, _H, _I64, _H, _I64, _D, _D, _INT],
     "kh_cheb_apply": [_H, _H, _H, _INT, _c_double_p, _H, _I64, _H, _I64, _I64, _H],
@@ -873,6 +876,32 @@ class Context(object):
             "kh_spai_build")
         return m, dict(n=buf[0], pnnz=buf[1], qmax=buf[2], group_width=buf[3], workgroups=buf[4], lds_bytes=buf[5],
                        first_broken_row=buf[7])
+
+    def fsai(self, A, P):
+        """The unscaled rows of the factorized sparse approximate inverse of the Hermitian positive definite SciPy CSR matrix
+        ``A`` on the lower-triangular pattern of the CSR matrix ``P`` (both with sorted, duplicate-free indices; every row of
+        ``P`` ends in its diagonal and has at most 32 entries), built on the device in one launch (``kh_fsai_build`` /
+        ``kh_zfsai_build``).  Returns ``(u, d, info)``: ``u`` at the CSR positions of ``P`` and the real ``d`` of length ``n``;
+        row ``i`` of ``G`` is ``u_i / sqrt(d_i)``.  Only the lower triangle of ``A`` is read.  A breakdown is not an error
+        here: ``info["first_broken_row"]`` names the row (-1: none)."""
+        if A.shape[0] != A.shape[1] or P.shape != A.shape:
+            raise BackendError("fsai: a square matrix and a pattern of its shape expected, got %s and %s" % (A.shape, P.shape))
+        indptr = numpy.ascontiguousarray(A.indptr, dtype=numpy.int32)
+        indices = numpy.ascontiguousarray(A.indices, dtype=numpy.int32)
+        pindptr = numpy.ascontiguousarray(P.indptr, dtype=numpy.int32)
+        pindices = numpy.ascontiguousarray(P.indices, dtype=numpy.int32)
+        dt = _block_dtype(A.dtype)
+        data = numpy.ascontiguousarray(A.data, dtype=dt)
+        u = numpy.empty(pindices.size, dtype=dt)
+        d = numpy.empty(A.shape[0], dtype=numpy.float64)
+        buf = (ctypes.c_int64 * 8)()
+        fn = self._lib.kh_zfsai_build if dt == _C128 else self._lib.kh_fsai_build
+        _check(self._lib, self._with_memory(lambda: fn(
+            self._h, A.shape[0], data.size, indptr.ctypes.data_as(_c_int32_p), indices.ctypes.data_as(_c_int32_p), _dptr(data),
+            pindices.size, pindptr.ctypes.data_as(_c_int32_p), pindices.ctypes.data_as(_c_int32_p), _dptr(u), _dptr(d), buf)),
+            "kh_fsai_build")
+        return u, d, dict(n=buf[0], pnnz=buf[1], qmax=buf[2], group_width=buf[3], workgroups=buf[4], lds_bytes=buf[5],
+                          first_broken_row=buf[7])
 
     def cheb_update(self, AZ, azcol, R, rcol, Dinv, D, dcol, Zin, zincol, Zout, zoutcol, a, b, first=False):
         """One composed step of the Chebyshev iteration on single columns (``kh_cheb_update``): ``first`` is step 0

@@ -1097,6 +1097,8 @@ int kh_ctx_get(kh_ctx ctx, const char* key, int64_t* value) {
     else if (!strcmp(key, "ilu0p_refactor_us")) *value = ctx->ilu0p_refactor_us;
     else if (!strcmp(key, "n_spai_build")) *value = ctx->n_spai_build;
     else if (!strcmp(key, "spai_device_us")) *value = ctx->spai_device_us;
+    else if (!strcmp(key, "n_fsai_build")) *value = ctx->n_fsai_build;
+    else if (!strcmp(key, "fsai_device_us")) *value = ctx->fsai_device_us;
     else if (!strcmp(key, "cheb_fused")) *value = ctx->cheb_fused;
     else if (!strcmp(key, "n_cheb_apply")) *value = ctx->n_cheb_apply;
     else if (!strcmp(key, "n_cheb_fused")) *value = ctx->n_cheb_fused;
