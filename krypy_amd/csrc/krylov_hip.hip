@@ -712,6 +712,9 @@ static int try_lowsync_mgs(kh_ctx ctx, kh_vec V, double* w, int64_t wld, int64_t
     return 1;
 }
 
+// k_cg_update writes one partial per workgroup of this grid from part_slot(SLOT_NRM): at most 2 * NB_MAX of them, which is
+// exactly what slot SLOT_NRM = MAXC + 2 and the spare slot behind it hold - the last two of the MAXC + 4 slots of NB_MAX
+// doubles in ctx->part (2 * NB_MAX <= (MAXC + 4 - SLOT_NRM) * NB_MAX; tests/test_csr_stream_host.py reads the constants).
 int grid_lin(kh_ctx ctx, int64_t n) {
     int64_t need = (n + BS - 1) / BS;
     if (need < 1) need = 1;
@@ -909,15 +912,12 @@ int kh_ctx_counters(kh_ctx ctx, int64_t out[4]) {
 
 int kh_ctx_tune(kh_ctx ctx, int reduce_blocks, int spmv_tile) {
     KH_ARG(ctx != nullptr, "kh_ctx_tune: NULL ctx");
-    if (reduce_blocks > 0) {
-        KH_ARG(reduce_blocks <= NB_MAX, "reduce_blocks %d > %d", reduce_blocks, NB_MAX);
-        ctx->nb = reduce_blocks;
-    }
-    if (spmv_tile > 0) {
-        KH_ARG(spmv_tile == 1024 || spmv_tile == 2048 || spmv_tile == 4096,
-               "spmv_tile %d must be 1024, 2048 or 4096", spmv_tile);
-        ctx->spmv_tile = spmv_tile;
-    }
+    // both arguments are judged before either setting moves: a call that fails changes nothing
+    KH_ARG(reduce_blocks <= NB_MAX, "reduce_blocks %d > %d", reduce_blocks, NB_MAX);
+    KH_ARG(spmv_tile <= 0 || spmv_tile == 1024 || spmv_tile == 2048 || spmv_tile == 4096,
+           "spmv_tile %d must be 1024, 2048 or 4096", spmv_tile);
+    if (reduce_blocks > 0) ctx->nb = reduce_blocks;
+    if (spmv_tile > 0) ctx->spmv_tile = spmv_tile;
     return 0;
 }
 

@@ -526,7 +526,9 @@ int kh_zcsr_upload(kh_ctx ctx, int64_t n_rows, int64_t n_cols, int64_t nnz, cons
     A->n_rows = n_rows;
     A->n_cols = n_cols;
     A->nnz = nnz;
-    A->tile = std::min(ctx->spmv_tile, 2048);   // double2 products: 32 KB of LDS at 2048
+    // double2 products: 32 KB of LDS at 2048.  A context tuned to 4096 uploads complex operators at 2048, so tile / BS is 4 or
+    // 8 here and `case 16` of zapply_one - k_zspmv_stream<16> - is never reached (tests/test_gpu_csr_stream.py holds both)
+    A->tile = std::min(ctx->spmv_tile, 2048);
     // row blocks: same greedy rule as the real kernel
     std::vector<int32_t> blk;
     blk.push_back(0);
