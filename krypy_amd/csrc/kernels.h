@@ -361,8 +361,9 @@ static __global__ __launch_bounds__(BS) void k_waxpby(int64_t n, double* z, doub
     }
 }
 
-static __global__ __launch_bounds__(BS) void k_vdiv(int64_t n, double* __restrict__ z,
-                                             const double* __restrict__ x, double s) {
+// z and x may be the same column (utils.py divides a reflector, a basis column and the columns of a QR factor in place): no
+// __restrict__ here.  Element i is read once and written once by the same lane (tests/test_gpu_panel.py holds the in-place form).
+static __global__ __launch_bounds__(BS) void k_vdiv(int64_t n, double* z, const double* x, double s) {
     const int64_t stride = (int64_t)gridDim.x * BS;
     for (int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x; i < n; i += stride) st_nt(z + i, x[i] / s);
 }

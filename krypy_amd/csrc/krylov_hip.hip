@@ -1272,7 +1272,11 @@ int kh_vec_copy(kh_vec dst, int64_t dcol, kh_vec src, int64_t scol, int64_t ncol
         return 0;
     }
     KH_ARG(dst->ld == src->ld || ncols == 1, "kh_vec_copy: blocks with different leading dimensions");
-    KH_HIP(hipMemcpyAsync(dst->col(dcol), src->col(scol), sizeof(double) * src->ld * ncols,
+    // One column between blocks padded differently (padded_ld follows the chain switches, so two blocks of one length
+    // allocated on either side of kh_ctx_set can differ): the shorter of the two columns.  Both hold the n rows and both
+    // paddings are zero, so nothing is lost - src->ld doubles ran over the head of column dcol + 1, or past the block.
+    const int64_t ld = std::min(src->ld, dst->ld);
+    KH_HIP(hipMemcpyAsync(dst->col(dcol), src->col(scol), sizeof(double) * ld * ncols,
                           hipMemcpyDeviceToDevice, dst->ctx->stream));
     return 0;
 }

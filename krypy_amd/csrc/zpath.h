@@ -658,7 +658,10 @@ int kh_zgemm_nn(kh_ctx ctx, kh_vec X, int64_t x0, int64_t k, const double* C, in
     double* dev = ctx->scal + ZSC_COEF;
     for (int64_t c = 0; c < nc; ++c) {
         if (k == 0) {
+            // Y = beta Y + X C with nothing to add: the scaling still happens, as in kh_gemm_nn (beta is real, so the real
+            // kernel on the (re, im) view; this branch used to return with Y unscaled for every beta but 0)
             if (beta == 0.0) KH_TRY(kh_vec_zero(Y, y0 + c, 1));
+            else if (beta != 1.0) KH_TRY(kh_waxpby(ctx, Y, y0 + c, beta, Y, y0 + c, 0.0, Y, y0 + c));
             continue;
         }
         for (int64_t i = 0; i < k; ++i) {
