@@ -859,23 +859,31 @@ class Context(object):
         (``kh_spai_build`` / ``kh_zspai_build``): row ``i`` minimises ``|| e_i^T - m^T A[J_i, :] ||_2`` over the pattern columns
         ``J_i``.  Returns ``(m_data, info)``: the values at the CSR positions of ``P`` and a dict.  A breakdown is not an error
         here: ``info["first_broken_row"]`` names the row (-1: none)."""
+        (m,), info = self._sai_build("spai", A, P, per_row=False)
+        return m, info
+
+    def _sai_build(self, name, A, P, per_row):
+        """The call of ``kh_<name>_build`` / ``kh_z<name>_build`` for :meth:`spai` and :meth:`fsai`: ``(outputs, info)`` with
+        the values at the CSR positions of ``P`` and, with ``per_row``, one real value per row after them."""
         if A.shape[0] != A.shape[1] or P.shape != A.shape:
-            raise BackendError("spai: a square matrix and a pattern of its shape expected, got %s and %s" % (A.shape, P.shape))
+            raise BackendError("%s: a square matrix and a pattern of its shape expected, got %s and %s" % (name, A.shape, P.shape))
         indptr = numpy.ascontiguousarray(A.indptr, dtype=numpy.int32)
         indices = numpy.ascontiguousarray(A.indices, dtype=numpy.int32)
         pindptr = numpy.ascontiguousarray(P.indptr, dtype=numpy.int32)
         pindices = numpy.ascontiguousarray(P.indices, dtype=numpy.int32)
         dt = _block_dtype(A.dtype)
         data = numpy.ascontiguousarray(A.data, dtype=dt)
-        m = numpy.empty(pindices.size, dtype=dt)
+        outs = [numpy.empty(pindices.size, dtype=dt)]
+        if per_row:
+            outs.append(numpy.empty(A.shape[0], dtype=numpy.float64))
         buf = (ctypes.c_int64 * 8)()
-        fn = self._lib.kh_zspai_build if dt == _C128 else self._lib.kh_spai_build
+        fn = getattr(self._lib, "kh_%s%s_build" % ("z" if dt == _C128 else "", name))
         _check(self._lib, self._with_memory(lambda: fn(
             self._h, A.shape[0], data.size, indptr.ctypes.data_as(_c_int32_p), indices.ctypes.data_as(_c_int32_p), _dptr(data),
-            pindices.size, pindptr.ctypes.data_as(_c_int32_p), pindices.ctypes.data_as(_c_int32_p), _dptr(m), buf)),
-            "kh_spai_build")
-        return m, dict(n=buf[0], pnnz=buf[1], qmax=buf[2], group_width=buf[3], workgroups=buf[4], lds_bytes=buf[5],
-                       first_broken_row=buf[7])
+            pindices.size, pindptr.ctypes.data_as(_c_int32_p), pindices.ctypes.data_as(_c_int32_p), *[_dptr(o) for o in outs], buf)),
+            "kh_%s_build" % name)
+        return outs, dict(n=buf[0], pnnz=buf[1], qmax=buf[2], group_width=buf[3], workgroups=buf[4], lds_bytes=buf[5],
+                          first_broken_row=buf[7])
 
     def fsai(self, A, P):
         """The unscaled rows of the factorized sparse approximate inverse of the Hermitian positive definite SciPy CSR matrix
@@ -884,24 +892,8 @@ class Context(object):
         ``kh_zfsai_build``).  Returns ``(u, d, info)``: ``u`` at the CSR positions of ``P`` and the real ``d`` of length ``n``;
         row ``i`` of ``G`` is ``u_i / sqrt(d_i)``.  Only the lower triangle of ``A`` is read.  A breakdown is not an error
         here: ``info["first_broken_row"]`` names the row (-1: none)."""
-        if A.shape[0] != A.shape[1] or P.shape != A.shape:
-            raise BackendError("fsai: a square matrix and a pattern of its shape expected, got %s and %s" % (A.shape, P.shape))
-        indptr = numpy.ascontiguousarray(A.indptr, dtype=numpy.int32)
-        indices = numpy.ascontiguousarray(A.indices, dtype=numpy.int32)
-        pindptr = numpy.ascontiguousarray(P.indptr, dtype=numpy.int32)
-        pindices = numpy.ascontiguousarray(P.indices, dtype=numpy.int32)
-        dt = _block_dtype(A.dtype)
-        data = numpy.ascontiguousarray(A.data, dtype=dt)
-        u = numpy.empty(pindices.size, dtype=dt)
-        d = numpy.empty(A.shape[0], dtype=numpy.float64)
-        buf = (ctypes.c_int64 * 8)()
-        fn = self._lib.kh_zfsai_build if dt == _C128 else self._lib.kh_fsai_build
-        _check(self._lib, self._with_memory(lambda: fn(
-            self._h, A.shape[0], data.size, indptr.ctypes.data_as(_c_int32_p), indices.ctypes.data_as(_c_int32_p), _dptr(data),
-            pindices.size, pindptr.ctypes.data_as(_c_int32_p), pindices.ctypes.data_as(_c_int32_p), _dptr(u), _dptr(d), buf)),
-            "kh_fsai_build")
-        return u, d, dict(n=buf[0], pnnz=buf[1], qmax=buf[2], group_width=buf[3], workgroups=buf[4], lds_bytes=buf[5],
-                          first_broken_row=buf[7])
+        (u, d), info = self._sai_build("fsai", A, P, per_row=True)
+        return u, d, info
 
     def cheb_update(self, AZ, azcol, R, rcol, Dinv, D, dcol, Zin, zincol, Zout, zoutcol, a, b, first=False):
         """One composed step of the Chebyshev iteration on single columns (``kh_cheb_update``): ``first`` is step 0

@@ -7,40 +7,29 @@
 // A[J, J] y = e_last up to the scale y_last = 1 / d_i: A[J, J] = L D L^H by a root-free Cholesky factorisation, then L^T u = e_last.
 // This header computes u and d_i; the square root and the division by it are the caller's (utils.fsai does them in NumPy).
 // THE CONTRACT (every multiply, add and divide rounds on its own; complex product (ac - bd, ad + bc); a complex value times or
-// over a real d: part by part - the rules of spai.h):
+// over a real d: part by part):
 //   S_ab (a >= b) = the stored A[J_a, J_b], or +0 where row J_a has no entry in column J_b: bits copied, no arithmetic - the merge of
 //                   the sorted CSR row J_a with J.  Only the LOWER triangle of A is ever read.
-//   for j = 0 .. q-1:   v_k = L_jk * d_k (k < j);   s = S_jj; s = s - L_jk * conj(v_k) (k < j ascending);   d_j = Re(s)
-//                       for i > j:  s = S_ij; s = s - L_ik * conj(v_k) (k < j ascending);  L_ij = s / d_j
+//   L, d: the factorisation of sai_row.h with X = S
 //   u_{q-1} = 1;   u_a = s with s = +0; s = s - L_ka * u_k (k = a + 1 .. q - 1 ascending, a = q - 2 .. 0)
 // The back substitution takes L UNCONJUGATED (L^T u = e_last): that is what makes (G A)[i, J_b] = 0 for b < q - 1 with complex data.
 // Outputs: u at the CSR positions of the pattern and d_i = d_{q-1}, one real value per row; a part that is a NaN is stored as the one
-// quiet NaN 0x7ff8000000000000 (khspai::stored).  A row breaks down when some d_j is not > 0 or not finite (A[J, J] is not positive
+// quiet NaN 0x7ff8000000000000 (khsai::stored).  A row breaks down when some d_j is not > 0 or not finite (A[J, J] is not positive
 // definite); the arithmetic goes on and the SMALLEST such row is reported.
 //
 // row<Z>() deals that work to the W lanes of a group in phases with a barrier between them (Exec::phase).  Every S_ab, L_ij and u_a
 // is the work of one lane in the order above, so the result does not depend on W:
 //   gather   matrix row a (the merge of CSR row J_a with J_0 .. J_a) to lane a mod W
-//   P1(j)    T_ij = S_ij - sum_{k<j} L_ik conj(v_k) for i >= j, lane (i - j) mod W;  d_j
-//   P2(j)    L_ij = T_ij / d_j for i > j, lane (i - j - 1) mod W; that lane of row j + 1 also writes v_j = L_{j+1,j} * d_j;
-//            v_k = L_{j+1,k} * d_k for k < j, lane k mod W: the v of column j + 1
+//   P1(j), P2(j)   those of sai_row.h (the same loop as in spai.h without its forward column; sai_row.h says why it stands in both)
 //   back     lane 0: the back substitution, u and d_i written to the output
 // The loops that hold a barrier run to `qloop`, the longest pattern row of the CALL, with j < q as a predicate: all lanes of a
-// workgroup reach every barrier.  Work space of one row: the layout of spai.h (khspai::row_doubles; P = 1 real / 2 complex planes,
-// S = qloop | 1 the odd row stride):
-//   [P * S * qloop] S / T / L in place, lower triangle   [qloop] d   [P * qloop] v   [P * qloop] u
+// workgroup reach every barrier.  Work space of one row: the layout of sai_row.h with X = S and x = u.
 #pragma once
-#include "spai.h"
+#include "sai_row.h"
 
 namespace khfsai {
 
-using khspai::broken;
-using khspai::Csr;
-using khspai::HostLanes;
-using khspai::QMAX;
-using khspai::row_doubles;
-using khspai::stored;
-using khspai::stride;
+using namespace khsai;      // QMAX, Csr, row_doubles, ...: what every row-by-row builder shares
 
 // lanes per pattern row for a call whose longest pattern row has qmax entries - measured (KERNELS.md 4.26: N = 10^6, q = 3, 7, 13,
 // 21, widths 8 / 16 / 32 / 64, real and complex).  The thresholds of khspai::group_width carry over for short rows; the gather here is
@@ -50,12 +39,7 @@ inline int group_width(int64_t qmax) { return qmax <= 8 ? 8 : qmax <= 16 ? 16 : 
 // Checks A and the pattern.  Returns "" and the longest pattern row, or what is wrong (the row named).
 inline std::string validate(int64_t n, int64_t nnz, const int32_t* indptr, const int32_t* indices, int64_t pnnz, const int32_t* pindptr,
                             const int32_t* pindices, int64_t* qmax) {
-    auto str = [](int64_t v) { return std::to_string((long long)v); };
-    if (n < 1 || n > (int64_t)0x7fffffff - 64) return "n = " + str(n) + " out of range";
-    int64_t longest = 0;
-    std::string why = khspai::check_pattern("A", n, nnz, indptr, indices, &longest);
-    if (!why.empty()) return why;
-    why = khspai::check_pattern("the pattern", n, pnnz, pindptr, pindices, qmax);
+    const std::string why = validate_patterns(n, nnz, indptr, indices, pnnz, pindptr, pindices, qmax);
     if (!why.empty()) return why;
     for (int64_t i = 0; i < n; ++i) {
         const int64_t q = pindptr[i + 1] - pindptr[i];
@@ -72,15 +56,10 @@ inline std::string validate(int64_t n, int64_t nnz, const int32_t* indptr, const
 // goes.  Returns true when a d_j this lane computed is not > 0 or not finite (the host form: any lane).  q = 0: nothing is read or
 // written, every barrier is reached.
 template <bool Z, class Exec>
-KH_SPAI_HD inline bool row(const Csr& A, const int32_t* J, int q, int qloop, double* w, double* u_out, double* d_out, int W, Exec& ex) {
-    const int S = stride(qloop), P = Z ? 2 : 1;
-    double* Lr = w;                                  // [a * S + b], lower triangle
-    double* Li = w + (Z ? S * qloop : 0);
-    double* d = w + P * S * qloop;
-    double* vr = d + qloop;
-    double* vi = vr + (Z ? qloop : 0);
-    double* ur = vr + P * qloop;
-    double* ui = ur + (Z ? qloop : 0);
+KH_SAI_HD inline bool row(const Csr& A, const int32_t* J, int q, int qloop, double* w, double* u_out, double* d_out, int W, Exec& ex) {
+    const Planes<Z> ws(w, qloop);
+    const int S = ws.S;
+    double *Lr = ws.Lr, *Li = ws.Li, *d = ws.d, *vr = ws.vr, *vi = ws.vi, *ur = ws.xr, *ui = ws.xi;
     bool bad = false;
 
     ex.phase([&](int lane) {          // gather
@@ -186,16 +165,10 @@ KH_SPAI_HD inline bool row(const Csr& A, const int32_t* J, int q, int qloop, dou
 // work: row_doubles(qloop, cplx) doubles.
 inline int64_t build_host(int64_t n, const Csr& A, const int32_t* pindptr, const int32_t* pindices, int qloop, int W, bool cplx,
                           double* work, double* u_out, double* d_out) {
-    int64_t bad = -1;
-    HostLanes ex{W};
-    for (int64_t i = 0; i < n; ++i) {
-        const int32_t p0 = pindptr[i];
-        const int q = pindptr[i + 1] - p0;
-        const bool broke = cplx ? row<true>(A, pindices + p0, q, qloop, work, u_out + 2 * (int64_t)p0, d_out + i, W, ex)
-                                : row<false>(A, pindices + p0, q, qloop, work, u_out + p0, d_out + i, W, ex);
-        if (broke && bad < 0) bad = i;
-    }
-    return bad;
+    return khsai::build_host(n, pindptr, W, [&](int64_t i, int32_t p0, int q, HostLanes& ex) {
+        return cplx ? row<true>(A, pindices + p0, q, qloop, work, u_out + 2 * (int64_t)p0, d_out + i, W, ex)
+                    : row<false>(A, pindices + p0, q, qloop, work, u_out + p0, d_out + i, W, ex);
+    });
 }
 
 }  // namespace khfsai

@@ -17,8 +17,8 @@
 // into one int32, read back once after the last launch.
 #include <new>
 
+#include "dev_owned.h"
 #include "ilu0.h"
-#include "kh_internal.h"
 
 using namespace kh;
 
@@ -57,36 +57,6 @@ __global__ __launch_bounds__(khtri::NARROW_MAX_THREADS) void k_ilu0_narrow(Ilu0D
     }
 }
 
-// what one call holds on the device; released on every way out
-struct Ilu0Mem {
-    int32_t *indptr = nullptr, *indices = nullptr, *dpos = nullptr, *row_id = nullptr, *lev_slice = nullptr, *bad = nullptr;
-    double* a = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    ~Ilu0Mem() {
-        (void)hipFree(indptr);
-        (void)hipFree(indices);
-        (void)hipFree(dpos);
-        (void)hipFree(row_id);
-        (void)hipFree(lev_slice);
-        (void)hipFree(bad);
-        (void)hipFree(a);
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-    }
-};
-
-template <typename T>
-int to_device(const char* who, T** dst, const T* src, size_t count) {
-    const size_t bytes = sizeof(T) * std::max<size_t>(count, 1);
-    hipError_t e = hipMalloc(dst, bytes);
-    if (e != hipSuccess) {
-        *dst = nullptr;
-        return fail(KH_ERR_NOMEM, "%s: hipMalloc(%zu bytes): %s", who, bytes, hipGetErrorString(e));
-    }
-    if (count) KH_HIP(hipMemcpy(*dst, src, sizeof(T) * count, hipMemcpyHostToDevice));
-    return 0;
-}
-
 int ilu0_factor(kh_ctx ctx, int64_t n, int64_t nnz, const int32_t* indptr, const int32_t* indices, const double* data, double* lu_out,
                 int64_t info[8], int cplx) {
     const char* who = cplx ? "kh_zilu0_factor" : "kh_ilu0_factor";
@@ -101,43 +71,39 @@ int ilu0_factor(kh_ctx ctx, int64_t n, int64_t nnz, const int32_t* indptr, const
         KH_ARG(data != nullptr && lu_out != nullptr, "%s: NULL array", who);
         const int w = cplx ? 2 : 1;
         const int32_t none = 0x7fffffff;
-        Ilu0Mem m;
-        KH_TRY(to_device(who, &m.indptr, indptr, (size_t)n + 1));
-        KH_TRY(to_device(who, &m.indices, indices, (size_t)nnz));
-        KH_TRY(to_device(who, &m.a, data, (size_t)nnz * w));
-        KH_TRY(to_device(who, &m.dpos, p.dpos.data(), p.dpos.size()));
-        KH_TRY(to_device(who, &m.row_id, p.row_id.data(), p.row_id.size()));
-        KH_TRY(to_device(who, &m.lev_slice, p.lev_slice.data(), p.lev_slice.size()));
-        KH_TRY(to_device(who, &m.bad, &none, 1));
-        KH_HIP(hipEventCreate(&m.ev0));
-        KH_HIP(hipEventCreate(&m.ev1));
-        const Ilu0Dev d{m.indptr, m.indices, m.dpos, m.row_id, m.bad};
-        KH_HIP(hipEventRecord(m.ev0, ctx->stream));
+        DevArray<int32_t> dev_indptr, dev_indices, dpos, row_id, lev_slice, bad_word;
+        DevArray<double> a;
+        EventPair ev;
+        KH_TRY(to_device(who, dev_indptr, indptr, (size_t)n + 1));
+        KH_TRY(to_device(who, dev_indices, indices, (size_t)nnz));
+        KH_TRY(to_device(who, a, data, (size_t)nnz * w));
+        KH_TRY(to_device(who, dpos, p.dpos.data(), p.dpos.size()));
+        KH_TRY(to_device(who, row_id, p.row_id.data(), p.row_id.size()));
+        KH_TRY(to_device(who, lev_slice, p.lev_slice.data(), p.lev_slice.size()));
+        KH_TRY(to_device(who, bad_word, &none, 1));
+        const Ilu0Dev d{dev_indptr.get(), dev_indices.get(), dpos.get(), row_id.get(), bad_word.get()};
+        KH_TRY(ev.start(ctx->stream));
         for (const khtri::Launch& L : p.launches) {
             if (L.narrow) {
                 if (cplx)
-                    hipLaunchKernelGGL(k_ilu0_narrow<true>, dim3(1), dim3(L.threads), 0, ctx->stream, d, m.lev_slice, L.lev0, L.nlev, m.a);
+                    hipLaunchKernelGGL(k_ilu0_narrow<true>, dim3(1), dim3(L.threads), 0, ctx->stream, d, lev_slice.get(), L.lev0, L.nlev, a.get());
                 else
-                    hipLaunchKernelGGL(k_ilu0_narrow<false>, dim3(1), dim3(L.threads), 0, ctx->stream, d, m.lev_slice, L.lev0, L.nlev, m.a);
+                    hipLaunchKernelGGL(k_ilu0_narrow<false>, dim3(1), dim3(L.threads), 0, ctx->stream, d, lev_slice.get(), L.lev0, L.nlev, a.get());
                 ctx->n_ilu0_narrow += 1;
             } else {
                 const unsigned grid = (unsigned)((L.nslices + khtri::WIDE_WAVES - 1) / khtri::WIDE_WAVES);
                 if (cplx)
-                    hipLaunchKernelGGL(k_ilu0_wide<true>, dim3(grid), dim3(L.threads), 0, ctx->stream, d, L.slice0, L.nslices, m.a);
+                    hipLaunchKernelGGL(k_ilu0_wide<true>, dim3(grid), dim3(L.threads), 0, ctx->stream, d, L.slice0, L.nslices, a.get());
                 else
-                    hipLaunchKernelGGL(k_ilu0_wide<false>, dim3(grid), dim3(L.threads), 0, ctx->stream, d, L.slice0, L.nslices, m.a);
+                    hipLaunchKernelGGL(k_ilu0_wide<false>, dim3(grid), dim3(L.threads), 0, ctx->stream, d, L.slice0, L.nslices, a.get());
                 ctx->n_ilu0_wide += 1;
             }
         }
         KH_HIP(hipGetLastError());
-        KH_HIP(hipEventRecord(m.ev1, ctx->stream));
-        KH_HIP(hipEventSynchronize(m.ev1));
-        float ms = 0.f;
-        KH_HIP(hipEventElapsedTime(&ms, m.ev0, m.ev1));
-        ctx->ilu0_device_us = (int64_t)((double)ms * 1000.0);
+        KH_TRY(ev.stop(ctx->stream, &ctx->ilu0_device_us));
         int32_t bad = none;
-        KH_HIP(hipMemcpy(&bad, m.bad, sizeof(bad), hipMemcpyDeviceToHost));
-        if (nnz) KH_HIP(hipMemcpy(lu_out, m.a, sizeof(double) * (size_t)nnz * w, hipMemcpyDeviceToHost));
+        KH_HIP(hipMemcpy(&bad, bad_word.get(), sizeof(bad), hipMemcpyDeviceToHost));
+        if (nnz) KH_HIP(hipMemcpy(lu_out, a.get(), sizeof(double) * (size_t)nnz * w, hipMemcpyDeviceToHost));
         ctx->n_ilu0_factor += 1;
         const int64_t out[8] = {n, nnz, p.nlevels, p.n_wide, p.n_narrow, p.widest, p.longest, bad == none ? -1 : (int64_t)bad};
         for (int i = 0; i < 8; ++i) info[i] = out[i];

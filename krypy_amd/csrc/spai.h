@@ -7,84 +7,37 @@
 // factorisation G = L D L^H.  THE CONTRACT (every multiply, add and divide rounds on its own; complex product (ac - bd, ad + bc);
 // a complex value times or over a real d: part by part):
 //   G_ab (a >= b): two-pointer merge of the CSR rows J_a, J_b in ascending column, s = +0; s = s + conj(x) * y
-//   for j = 0 .. q-1:   v_k = L_jk * d_k (k < j);   s = G_jj; s = s - L_jk * conj(v_k) (k < j ascending);   d_j = Re(s)
-//                       for i > j:  s = G_ij; s = s - L_ik * conj(v_k) (k < j ascending);  L_ij = s / d_j
+//   L, d: the factorisation of sai_row.h with X = G
 //   y_a = r_a - sum_{k < a} L_ak * y_k (k ascending);  z_a = y_a / d_a;  m_a = z_a - sum_{k > a} conj(L_ka) * m_k (k ascending,
 //   a = q-1 .. 0)
-// A row breaks down when some d_j is not > 0 or not finite; the arithmetic goes on and the SMALLEST such row is reported.  IEEE 754
-// leaves the sign and payload of a NaN that an invalid operation produces to the hardware (inf - inf is 0x7ff8... on gfx950 and
-// 0xfff8... on x86), so a part of m_a that is a NaN is STORED as the quiet NaN 0x7ff8000000000000: host and device then agree in
-// every bit of a broken row too (infinities keep their sign; a NaN never turns into anything else on the way).
+// A row breaks down when some d_j is not > 0 or not finite; the arithmetic goes on and the SMALLEST such row is reported.  A part of
+// m_a that is a NaN is STORED as the quiet NaN 0x7ff8000000000000 (sai_row.h says why): host and device agree in every bit of a
+// broken row too.
 //
 // row<Z>() deals that work to the W lanes of a group in phases with a barrier between them (Exec::phase).  Every G_ab, L_ij, y_a
 // and m_a is the work of one lane in the order above, so the result does not depend on W:
 //   gram     pair t = a (a + 1) / 2 + b to lane t mod W;  r_a to lane a mod W
 //   P1(j)    y_a = y_a - L_{a,j-1} * y_{j-1} for a >= j, lane a mod W (the forward substitution, column by column: every y_a still
-//            receives its terms in ascending k);  T_ij = G_ij - sum_{k<j} L_ik conj(v_k) for i >= j, lane (i - j) mod W;  d_j
-//   P2(j)    L_ij = T_ij / d_j for i > j, lane (i - j - 1) mod W; that lane of row j + 1 also writes v_j = L_{j+1,j} * d_j;
-//            v_k = L_{j+1,k} * d_k for k < j, lane k mod W: the v of column j + 1
+//            receives its terms in ascending k), then P1(j) of sai_row.h
+//   P2(j)    that of sai_row.h (the same loop as in fsai.h; sai_row.h says why it stands in both)
 //   back     lane 0: z and the back substitution, m written to the output
 // The loops that hold a barrier run to `qloop`, the longest pattern row of the CALL, with j < q as a predicate: all lanes of a
-// workgroup reach every barrier.  Work space of one row (doubles, P = 1 real / 2 complex planes, S = qloop | 1 the row stride -
-// odd, so the lanes of P1, one matrix row each, read 32 different LDS banks with 64-bit reads):
-//   [P * S * qloop] G / T / L in place, lower triangle   [qloop] d   [P * qloop] v   [P * qloop] r / y
+// workgroup reach every barrier.  Work space of one row: the layout of sai_row.h with X = G and x = r / y.
 #pragma once
-#include <float.h>
-#include <math.h>
-#include <stdint.h>
-
-#include <string>
-
-#if defined(__HIPCC__)
-#define KH_SPAI_HD __host__ __device__
-#else
-#define KH_SPAI_HD
-#endif
+#include "sai_row.h"
 
 namespace khspai {
 
-constexpr int QMAX = 32;
+using namespace khsai;      // QMAX, Csr, row_doubles, ...: what every row-by-row builder shares
 
-KH_SPAI_HD inline int stride(int qloop) { return qloop | 1; }
-// doubles of one row's work space
-KH_SPAI_HD inline int64_t row_doubles(int qloop, bool cplx) {
-    const int P = cplx ? 2 : 1;
-    return (int64_t)P * stride(qloop) * qloop + qloop + 2 * (int64_t)P * qloop;
-}
 // lanes per pattern row for a call whose longest pattern row has qmax entries - measured (KERNELS.md 4.24: N = 10^6, q = 5, 13, 25,
 // widths 8 / 16 / 32 / 64): short rows want many rows per workgroup and barrier, long ones lanes for the q (q + 1) / 2 merges
 inline int group_width(int64_t qmax, bool cplx) { return qmax <= 8 ? 8 : qmax <= 16 ? 16 : cplx ? 64 : 32; }
 
-// one CSR pattern: sorted, duplicate-free, columns in [0, n).  `what` names it in the message ("A" / "the pattern").
-inline std::string check_pattern(const char* what, int64_t n, int64_t nnz, const int32_t* indptr, const int32_t* indices, int64_t* longest) {
-    auto str = [](int64_t v) { return std::to_string((long long)v); };
-    if (nnz < 0 || nnz > (int64_t)0x7fffffff) return std::string("nnz = ") + str(nnz) + " of " + what + " out of range (int32 row pointers)";
-    if (!indptr || (nnz > 0 && !indices)) return std::string("NULL array of ") + what;
-    if (indptr[0] != 0 || indptr[n] != nnz) return std::string("indptr[0] != 0 or indptr[n] != nnz of ") + what;
-    *longest = 0;
-    for (int64_t i = 0; i < n; ++i) {
-        const int64_t a = indptr[i], b = indptr[i + 1];
-        if (a > b || b > nnz) return std::string("indptr of ") + what + " not ascending at row " + str(i);
-        for (int64_t p = a; p < b; ++p) {
-            const int64_t c = indices[p];
-            if (c < 0 || c >= n) return "column " + str(c) + " out of range in row " + str(i) + " of " + what;
-            if (p > a && indices[p - 1] >= c)
-                return std::string(indices[p - 1] == c ? "duplicate" : "unsorted") + " column indices in row " + str(i) + " of " + what;
-        }
-        if (b - a > *longest) *longest = b - a;
-    }
-    return "";
-}
-
 // Checks A and the pattern.  Returns "" and the longest pattern row, or what is wrong (the row named).
 inline std::string validate(int64_t n, int64_t nnz, const int32_t* indptr, const int32_t* indices, int64_t pnnz, const int32_t* pindptr,
                             const int32_t* pindices, int64_t* qmax) {
-    auto str = [](int64_t v) { return std::to_string((long long)v); };
-    if (n < 1 || n > (int64_t)0x7fffffff - 64) return "n = " + str(n) + " out of range";
-    int64_t longest = 0;
-    std::string why = check_pattern("A", n, nnz, indptr, indices, &longest);
-    if (!why.empty()) return why;
-    why = check_pattern("the pattern", n, pnnz, pindptr, pindices, qmax);
+    const std::string why = validate_patterns(n, nnz, indptr, indices, pnnz, pindptr, pindices, qmax);
     if (!why.empty()) return why;
     if (*qmax > QMAX)
         for (int64_t i = 0; i < n; ++i)
@@ -93,41 +46,17 @@ inline std::string validate(int64_t n, int64_t nnz, const int32_t* indptr, const
     return "";
 }
 
-struct Csr {
-    const int32_t* indptr;
-    const int32_t* indices;
-    const double* data;      // Z: (re, im) pairs
-};
-
-// The lanes of one group on the host, one after the other; the end of the loop is the barrier.
-struct HostLanes {
-    int W;
-    template <class F>
-    void phase(F f) {
-        for (int l = 0; l < W; ++l) f(l);
-    }
-};
-
-KH_SPAI_HD inline bool broken(double d) { return !(d > 0.0) || !(d <= DBL_MAX); }
-// what is stored for x: a NaN as the one quiet NaN 0x7ff8000000000000
-KH_SPAI_HD inline double stored(double x) { return x != x ? __builtin_nan("") : x; }
-
 // Row i of M on the W lanes of `ex` (a lane calls phase(f) with f(lane); phase() ends with the barrier).  J: the q pattern columns
 // of the row, w: row_doubles(qloop) of work space, m: where the q values go (Z: pairs).  Returns true when a d_j this lane
 // computed is not > 0 or not finite (the host form: any lane).  q = 0: nothing is read or written, every barrier is reached.
 template <bool Z, class Exec>
-KH_SPAI_HD inline bool row(const Csr& A, const int32_t* J, int q, int qloop, int32_t i, double* w, double* m, int W, Exec& ex) {
-    const int S = stride(qloop), P = Z ? 2 : 1;
-    double* Lr = w;                                  // [a * S + b], lower triangle
-    double* Li = w + (Z ? S * qloop : 0);
-    double* d = w + P * S * qloop;
-    double* vr = d + qloop;
-    double* vi = vr + (Z ? qloop : 0);
-    double* yr = vr + P * qloop;
-    double* yi = yr + (Z ? qloop : 0);
+KH_SAI_HD inline bool row(const Csr& A, const int32_t* J, int q, int qloop, int32_t i, double* w, double* m, int W, Exec& ex) {
+    const Planes<Z> ws(w, qloop);
+    const int S = ws.S;
+    double *Lr = ws.Lr, *Li = ws.Li, *d = ws.d, *vr = ws.vr, *vi = ws.vi, *yr = ws.xr, *yi = ws.xi;
     bool bad = false;
 
-    ex.phase([&](int lane) {
+    ex.phase([&](int lane) {          // gram
         const int npair = q * (q + 1) / 2;
         for (int t = lane; t < npair; t += W) {
             int a = (int)((sqrtf(8.0f * (float)t + 1.0f) - 1.0f) * 0.5f);
@@ -258,16 +187,10 @@ KH_SPAI_HD inline bool row(const Csr& A, const int32_t* J, int q, int qloop, int
 // work: row_doubles(qloop, cplx) doubles.
 inline int64_t build_host(int64_t n, const Csr& A, const int32_t* pindptr, const int32_t* pindices, int qloop, int W, bool cplx,
                           double* work, double* m_out) {
-    int64_t bad = -1;
-    HostLanes ex{W};
-    for (int64_t i = 0; i < n; ++i) {
-        const int32_t p0 = pindptr[i];
-        const int q = pindptr[i + 1] - p0;
-        const bool broke = cplx ? row<true>(A, pindices + p0, q, qloop, (int32_t)i, work, m_out + 2 * (int64_t)p0, W, ex)
-                                : row<false>(A, pindices + p0, q, qloop, (int32_t)i, work, m_out + p0, W, ex);
-        if (broke && bad < 0) bad = i;
-    }
-    return bad;
+    return khsai::build_host(n, pindptr, W, [&](int64_t i, int32_t p0, int q, HostLanes& ex) {
+        return cplx ? row<true>(A, pindices + p0, q, qloop, (int32_t)i, work, m_out + 2 * (int64_t)p0, W, ex)
+                    : row<false>(A, pindices + p0, q, qloop, (int32_t)i, work, m_out + p0, W, ex);
+    });
 }
 
 }  // namespace khspai

@@ -7,26 +7,12 @@
 // khspai::row are separated by __syncthreads().  The loops that hold a barrier run to qloop for every row, shorter rows and the
 // rows past n (q = 0) predicated: every thread reaches every barrier.  No kernel waits for another workgroup: no flags, no
 // spins.  A breakdown is an atomicMin of the row index into one int32, read back once after the launch.
-#include <new>
-
-#include "kh_internal.h"
+#include "sai_build.h"
 #include "spai.h"
 
 using namespace kh;
 
 namespace {
-
-constexpr int SPAI_THREADS = 256;
-constexpr int64_t SPAI_LDS_MAX = 64 * 1024;      // static limit of a workgroup without an opt-in
-
-struct DevLanes {
-    int lane;
-    template <class F>
-    __device__ __forceinline__ void phase(F f) {
-        f(lane);
-        __syncthreads();
-    }
-};
 
 struct SpaiDev {
     const int32_t* indptr;
@@ -40,7 +26,7 @@ struct SpaiDev {
 };
 
 template <bool Z, int W>
-__global__ __launch_bounds__(SPAI_THREADS) void k_spai(SpaiDev d) {
+__global__ __launch_bounds__(khsai::THREADS) void k_spai(SpaiDev d) {
     extern __shared__ double spai_lds[];
     const int g = threadIdx.x / W;
     const int64_t i = (int64_t)blockIdx.x * (blockDim.x / W) + g;
@@ -48,7 +34,7 @@ __global__ __launch_bounds__(SPAI_THREADS) void k_spai(SpaiDev d) {
     const int32_t p0 = live ? d.pindptr[i] : 0;
     const int q = live ? d.pindptr[i + 1] - p0 : 0;
     const khspai::Csr A{d.indptr, d.indices, d.data};
-    DevLanes ex{(int)(threadIdx.x % W)};
+    khsai::DevLanes ex{(int)(threadIdx.x % W)};
     if (khspai::row<Z>(A, d.pindices + p0, q, d.qloop, (int32_t)i, spai_lds + (int64_t)g * d.row_doubles, d.m + (Z ? 2 : 1) * (int64_t)p0, W, ex))
         atomicMin(d.bad, (int32_t)i);
 }
@@ -59,93 +45,34 @@ void launch(bool cplx, dim3 grid, dim3 block, size_t lds, hipStream_t stream, co
     else hipLaunchKernelGGL((k_spai<false, W>), grid, block, lds, stream, d);
 }
 
-// what one call holds on the device; released on every way out
-struct SpaiMem {
-    int32_t *indptr = nullptr, *indices = nullptr, *pindptr = nullptr, *pindices = nullptr, *bad = nullptr;
-    double *data = nullptr, *m = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    ~SpaiMem() {
-        (void)hipFree(indptr);
-        (void)hipFree(indices);
-        (void)hipFree(pindptr);
-        (void)hipFree(pindices);
-        (void)hipFree(bad);
-        (void)hipFree(data);
-        (void)hipFree(m);
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-    }
-};
-
-template <typename T>
-int to_device(const char* who, T** dst, const T* src, size_t count) {
-    const size_t bytes = sizeof(T) * std::max<size_t>(count, 1);
-    hipError_t e = hipMalloc(dst, bytes);
-    if (e != hipSuccess) {
-        *dst = nullptr;
-        return fail(KH_ERR_NOMEM, "%s: hipMalloc(%zu bytes): %s", who, bytes, hipGetErrorString(e));
-    }
-    if (count && src) KH_HIP(hipMemcpy(*dst, src, sizeof(T) * count, hipMemcpyHostToDevice));
-    return 0;
-}
-
 int spai_build(kh_ctx ctx, int64_t n, int64_t nnz, const int32_t* indptr, const int32_t* indices, const double* data, int64_t pnnz,
                const int32_t* pindptr, const int32_t* pindices, double* m_out, int64_t info[8], int cplx) {
     const char* who = cplx ? "kh_zspai_build" : "kh_spai_build";
-    KH_ARG(ctx != nullptr && info != nullptr, "%s: NULL", who);
-    if (kh_multi(ctx) || ctx->comm != nullptr)
-        return fail(KH_ERR_UNSUPPORTED, "%s: the context has a communicator - a row of the approximate inverse reads rows of A that "
-                                        "other ranks hold, sharded construction is not implemented", who);
-    try {
-        int64_t qmax = 0;
-        const std::string why = khspai::validate(n, nnz, indptr, indices, pnnz, pindptr, pindices, &qmax);
-        KH_ARG(why.empty(), "%s: %s", who, why.c_str());
-        KH_ARG((nnz == 0 || data != nullptr) && (pnnz == 0 || m_out != nullptr), "%s: NULL array", who);
-        const int w = cplx ? 2 : 1;
-        const int32_t none = 0x7fffffff;
-        const int qloop = (int)qmax;
-        const int W = khspai::group_width(qmax, cplx != 0);
-        const int64_t row_doubles = khspai::row_doubles(qloop, cplx != 0);
-        int rows = SPAI_THREADS / W;
-        while (rows > 1 && rows * row_doubles * (int64_t)sizeof(double) > SPAI_LDS_MAX) --rows;
-        const int64_t lds = rows * row_doubles * (int64_t)sizeof(double);
-        const int64_t grid = (n + rows - 1) / rows;
-        SpaiMem m;
-        KH_TRY(to_device(who, &m.indptr, indptr, (size_t)n + 1));
-        KH_TRY(to_device(who, &m.indices, indices, (size_t)nnz));
-        KH_TRY(to_device(who, &m.data, data, (size_t)nnz * w));
-        KH_TRY(to_device(who, &m.pindptr, pindptr, (size_t)n + 1));
-        KH_TRY(to_device(who, &m.pindices, pindices, (size_t)pnnz));
-        KH_TRY(to_device<double>(who, &m.m, nullptr, (size_t)pnnz * w));
-        KH_TRY(to_device(who, &m.bad, &none, 1));
-        KH_HIP(hipEventCreate(&m.ev0));
-        KH_HIP(hipEventCreate(&m.ev1));
-        const SpaiDev d{m.indptr, m.indices, m.data, m.pindptr, m.pindices, m.m, m.bad, (int32_t)n, qloop, (int32_t)row_doubles};
-        KH_HIP(hipEventRecord(m.ev0, ctx->stream));
-        if (qloop > 0) {
-            const dim3 g((unsigned)grid), b((unsigned)(rows * W));
+    const khsai::Call call{ctx, n, nnz, indptr, indices, data, pnnz, pindptr, pindices, info, cplx};
+    const khsai::Output outs[] = {{m_out, (size_t)pnnz * (cplx ? 2 : 1)}};
+    int64_t device_us = 0;
+    KH_TRY(khsai::build(
+        who, "the context has a communicator - a row of the approximate inverse reads rows of A that other ranks hold, sharded "
+             "construction is not implemented",
+        call, outs, &device_us,
+        [&](int64_t* qmax, int* W) {
+            const std::string why = khspai::validate(n, nnz, indptr, indices, pnnz, pindptr, pindices, qmax);
+            KH_ARG(why.empty(), "%s: %s", who, why.c_str());
+            KH_ARG((nnz == 0 || data != nullptr) && (pnnz == 0 || m_out != nullptr), "%s: NULL array", who);
+            *W = khspai::group_width(*qmax, cplx != 0);
+            return 0;
+        },
+        [&](const khsai::DevArgs& a, int W, dim3 g, dim3 b, size_t lds, hipStream_t stream) {
+            const SpaiDev d{a.indptr, a.indices, a.data, a.pindptr, a.pindices, a.out[0], a.bad, a.n, a.qloop, a.row_doubles};
             switch (W) {
-                case 8: launch<8>(cplx != 0, g, b, (size_t)lds, ctx->stream, d); break;
-                case 16: launch<16>(cplx != 0, g, b, (size_t)lds, ctx->stream, d); break;
-                case 32: launch<32>(cplx != 0, g, b, (size_t)lds, ctx->stream, d); break;
-                default: launch<64>(cplx != 0, g, b, (size_t)lds, ctx->stream, d); break;
+                case 8: launch<8>(cplx != 0, g, b, lds, stream, d); break;
+                case 16: launch<16>(cplx != 0, g, b, lds, stream, d); break;
+                case 32: launch<32>(cplx != 0, g, b, lds, stream, d); break;
+                default: launch<64>(cplx != 0, g, b, lds, stream, d); break;
             }
-            KH_HIP(hipGetLastError());
-        }
-        KH_HIP(hipEventRecord(m.ev1, ctx->stream));
-        KH_HIP(hipEventSynchronize(m.ev1));
-        float ms = 0.f;
-        KH_HIP(hipEventElapsedTime(&ms, m.ev0, m.ev1));
-        ctx->spai_device_us = (int64_t)((double)ms * 1000.0);
-        int32_t bad = none;
-        KH_HIP(hipMemcpy(&bad, m.bad, sizeof(bad), hipMemcpyDeviceToHost));
-        if (pnnz) KH_HIP(hipMemcpy(m_out, m.m, sizeof(double) * (size_t)pnnz * w, hipMemcpyDeviceToHost));
-        ctx->n_spai_build += 1;
-        const int64_t out[8] = {n, pnnz, qmax, W, qloop > 0 ? grid : 0, lds, 0, bad == none ? -1 : (int64_t)bad};
-        for (int i = 0; i < 8; ++i) info[i] = out[i];
-    } catch (const std::bad_alloc&) {
-        return fail(KH_ERR_NOMEM, "%s: out of host memory", who);
-    }
+        }));
+    ctx->spai_device_us = device_us;
+    ctx->n_spai_build += 1;
     return 0;
 }
 

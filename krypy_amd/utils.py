@@ -1280,6 +1280,33 @@ def _spai_matrix(A, what):
     return A
 
 
+def _sai_square(A):
+    """``A`` as a square canonical CSR matrix of float64 or complex128 (float32 / complex64 widened)."""
+    A = _spai_matrix(A, "A")
+    if A.shape[0] != A.shape[1]:
+        raise ArgumentError("a square matrix expected, got shape %s" % (A.shape,))
+    if A.dtype not in (numpy.dtype(numpy.float64), numpy.dtype(numpy.complex128)):
+        A = A.astype(_bdt(A.dtype))
+    return A
+
+
+def _sai_pattern(A, pattern):
+    """The pattern argument as a canonical CSR matrix of ``A``'s shape: ``A`` itself for None, otherwise the pattern of a sparse
+    matrix (stored zeros kept) or the nonzeros of a dense one."""
+    if pattern is None:
+        return A
+    if isinstance(pattern, MatrixLinearOperator) or _is_sparse(pattern):
+        P = _spai_matrix(pattern, "pattern")
+    else:
+        pattern = numpy.asarray(pattern)
+        if pattern.ndim != 2:
+            raise ArgumentError("pattern: a matrix expected, got an array of shape %s" % (pattern.shape,))
+        P = _spai_matrix(pattern != 0, "pattern")
+    if P.shape != A.shape:
+        raise ArgumentError("a pattern of shape %s expected, got %s" % (A.shape, P.shape))
+    return P
+
+
 def spai(A, pattern=None, side="left", symmetric=False):
     """The sparse approximate inverse of ``A`` on a fixed pattern (static-pattern SPAI), built on the device in one launch
     (``Context.spai``): a ``scipy.sparse.csr_matrix`` ``M`` with ``M.info`` (a dict).  A preconditioner given as a matrix: as
@@ -1302,23 +1329,8 @@ def spai(A, pattern=None, side="left", symmetric=False):
     dependent)."""
     if side not in ("left", "right"):
         raise ArgumentError("side %r: 'left' or 'right' expected" % (side,))
-    A = _spai_matrix(A, "A")
-    if A.shape[0] != A.shape[1]:
-        raise ArgumentError("a square matrix expected, got shape %s" % (A.shape,))
-    if A.dtype not in (numpy.dtype(numpy.float64), numpy.dtype(numpy.complex128)):
-        A = A.astype(_bdt(A.dtype))
-    if pattern is None:
-        P = A
-    else:
-        if isinstance(pattern, MatrixLinearOperator) or _is_sparse(pattern):
-            P = _spai_matrix(pattern, "pattern")
-        else:
-            pattern = numpy.asarray(pattern)
-            if pattern.ndim != 2:
-                raise ArgumentError("pattern: a matrix expected, got an array of shape %s" % (pattern.shape,))
-            P = _spai_matrix(pattern != 0, "pattern")
-        if P.shape != A.shape:
-            raise ArgumentError("a pattern of shape %s expected, got %s" % (A.shape, P.shape))
+    A = _sai_square(A)
+    P = _sai_pattern(A, pattern)
     if side == "right":
         A = A.T.tocsr()
         A.sort_indices()
@@ -1355,18 +1367,7 @@ def spai_operator(A, **kw):
 
 def _fsai_pattern(A, pattern):
     """``tril(pattern or A)`` with the diagonal added, as a canonical CSR pattern (stored zeros kept)."""
-    if pattern is None:
-        P = A
-    else:
-        if isinstance(pattern, MatrixLinearOperator) or _is_sparse(pattern):
-            P = _spai_matrix(pattern, "pattern")
-        else:
-            pattern = numpy.asarray(pattern)
-            if pattern.ndim != 2:
-                raise ArgumentError("pattern: a matrix expected, got an array of shape %s" % (pattern.shape,))
-            P = _spai_matrix(pattern != 0, "pattern")
-        if P.shape != A.shape:
-            raise ArgumentError("a pattern of shape %s expected, got %s" % (A.shape, P.shape))
+    P = _sai_pattern(A, pattern)
     n = A.shape[0]
     rows = numpy.repeat(numpy.arange(n), numpy.diff(P.indptr))
     low = P.indices <= rows
@@ -1400,11 +1401,7 @@ def fsai(A, pattern=None, check=True):
     :class:`ArgumentError` for a matrix that is not square, a pattern of another shape, a pattern row with more than 32 entries
     in its lower triangle, with ``check=True`` a matrix that is not Hermitian, and a breakdown (``A`` is not positive definite:
     a principal submatrix that a pattern row selects has a pivot that is not positive)."""
-    A = _spai_matrix(A, "A")
-    if A.shape[0] != A.shape[1]:
-        raise ArgumentError("a square matrix expected, got shape %s" % (A.shape,))
-    if A.dtype not in (numpy.dtype(numpy.float64), numpy.dtype(numpy.complex128)):
-        A = A.astype(_bdt(A.dtype))
+    A = _sai_square(A)
     P = _fsai_pattern(A, pattern)
     long_rows = numpy.flatnonzero(numpy.diff(P.indptr) > _SPAI_MAX_ROW)
     if long_rows.size:

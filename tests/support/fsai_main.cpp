@@ -5,46 +5,12 @@
 // and compares the bits of u and d (memcmp: a NaN must be the very same NaN).  One line per case and W:
 //   <case>/<r|z>/<W> q=<longest pattern row> bad=<first broken row> bits=<ok|DIFFER>
 // then one line per refused input:  <name> refused: <message>.  Exit status 1 when any bits differ.
-#include <stdio.h>
-#include <string.h>
-
-#include <algorithm>
-#include <string>
-#include <vector>
-
+// The cases' matrices and the comparison are in sai_main.h, shared with spai_main.cpp.
 #include "fsai.h"
 
+#include "sai_main.h"
+
 namespace {
-
-struct Mat {
-    int64_t n = 0;
-    std::vector<int32_t> ptr, idx;
-    std::vector<double> val;      // real: one per entry; complex: pairs
-    int64_t nnz() const { return (int64_t)idx.size(); }
-};
-
-typedef std::vector<std::pair<std::pair<int32_t, int32_t>, double>> Triplets;
-
-uint64_t lcg_state = 4321;
-double lcg() {      // uniform in (-1, 1), deterministic
-    lcg_state = lcg_state * 6364136223846793005ull + 1442695040888963407ull;
-    return (double)((lcg_state >> 11) & ((1ull << 53) - 1)) / (double)(1ull << 52) - 1.0;
-}
-
-// entries (row, col, value) -> CSR, sorted (the entries are unique)
-Mat from_triplets(int64_t n, Triplets t) {
-    std::sort(t.begin(), t.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
-    Mat m;
-    m.n = n;
-    m.ptr.assign((size_t)n + 1, 0);
-    for (const auto& e : t) {
-        m.ptr[(size_t)e.first.first + 1] += 1;
-        m.idx.push_back(e.first.second);
-        m.val.push_back(e.second);
-    }
-    for (int64_t i = 0; i < n; ++i) m.ptr[(size_t)i + 1] += m.ptr[(size_t)i];
-    return m;
-}
 
 // five-point Laplacian minus `shift` on the diagonal
 Mat laplacian(int nx, int ny, double shift) {
@@ -81,22 +47,6 @@ Mat diagonal(int n) {
     return from_triplets(n, t);
 }
 
-// the pattern of A * B (values 1)
-Mat pattern_product(const Mat& A, const Mat& B) {
-    Triplets t;
-    for (int32_t i = 0; i < A.n; ++i) {
-        std::vector<int32_t> cols;
-        for (int32_t p = A.ptr[(size_t)i]; p < A.ptr[(size_t)i + 1]; ++p) {
-            const int32_t k = A.idx[(size_t)p];
-            cols.insert(cols.end(), B.idx.begin() + B.ptr[(size_t)k], B.idx.begin() + B.ptr[(size_t)k + 1]);
-        }
-        std::sort(cols.begin(), cols.end());
-        cols.erase(std::unique(cols.begin(), cols.end()), cols.end());
-        for (int32_t c : cols) t.push_back({{i, c}, 1.0});
-    }
-    return from_triplets(A.n, t);
-}
-
 // the lower triangle of a pattern with the diagonal added
 Mat lower(const Mat& P) {
     Triplets t;
@@ -113,7 +63,7 @@ Mat lower(const Mat& P) {
 }
 
 // Hermitian: the lower triangle gets a seeded imaginary part, the upper one its conjugate, the diagonal stays real
-Mat make_hermitian(const Mat& A) {
+Mat complex_case(const Mat& A) {
     Mat Z = A;
     Z.val.assign(2 * A.val.size(), 0.0);
     for (int32_t i = 0; i < A.n; ++i)
@@ -129,14 +79,6 @@ Mat make_hermitian(const Mat& A) {
         }
     return Z;
 }
-
-struct C {
-    double r, i;
-};
-C mul(C a, C b) { return {a.r * b.r - a.i * b.i, a.r * b.i + a.i * b.r}; }
-C cj(C a) { return {a.r, -a.i}; }
-C sub(C a, C b) { return {a.r - b.r, a.i - b.i}; }
-double canon(double x) { return x != x ? __builtin_nan("") : x; }          // a NaN is stored as 0x7ff8000000000000
 
 // A[r, c] by a linear search of row r: the bits, or +0
 bool find(const Mat& A, int32_t r, int32_t c, int32_t* at) {
@@ -216,53 +158,29 @@ bool plain_row_r(const Mat& A, const int32_t* J, int q, double* u, double* dout)
     return bad;
 }
 
-int failures = 0;
+// ---- the hooks of sai_main.h ----------------------------------------------------------------------------------------------
+std::string validate(int64_t n, int64_t nnz, const Mat& A, const Mat& P, int64_t* qmax) {
+    return khfsai::validate(n, nnz, A.ptr.data(), A.idx.data(), P.nnz(), P.ptr.data(), P.idx.data(), qmax);
+}
 
-void run_case(const char* name, const Mat& A, const Mat& P, bool cplx) {
-    int64_t qmax = 0;
-    const std::string why = khfsai::validate(A.n, A.nnz(), A.ptr.data(), A.idx.data(), P.nnz(), P.ptr.data(), P.idx.data(), &qmax);
-    if (!why.empty()) {
-        printf("%s/%s refused: %s\n", name, cplx ? "z" : "r", why.c_str());
-        failures += 1;
-        return;
-    }
-    const int w = cplx ? 2 : 1;
-    std::vector<double> want((size_t)P.nnz() * w + 1, -7.0), dwant((size_t)A.n + 1, -7.0);
-    int64_t bad_want = -1;
-    for (int64_t i = 0; i < A.n; ++i) {
-        const int32_t p0 = P.ptr[(size_t)i];
-        const int q = P.ptr[(size_t)i + 1] - p0;
-        const bool b = cplx ? plain_row_z(A, P.idx.data() + p0, q, want.data() + 2 * (size_t)p0, dwant.data() + i)
-                            : plain_row_r(A, P.idx.data() + p0, q, want.data() + p0, dwant.data() + i);
-        if (b && bad_want < 0) bad_want = i;
-    }
+Outputs blank_outputs(const Mat& A, const Mat& P, bool cplx) {      // u and d
+    return {std::vector<double>((size_t)P.nnz() * (cplx ? 2 : 1) + 1, -7.0), std::vector<double>((size_t)A.n + 1, -7.0)};
+}
+
+bool plain_row(const Mat& A, const int32_t* J, int q, int64_t i, int32_t p0, bool cplx, Outputs& want) {
+    return cplx ? plain_row_z(A, J, q, want[0].data() + 2 * (size_t)p0, want[1].data() + i)
+                : plain_row_r(A, J, q, want[0].data() + p0, want[1].data() + i);
+}
+
+int64_t lanes_build(const Mat& A, const Mat& P, int qmax, int W, bool cplx, double* work, Outputs& got) {
     const khfsai::Csr csr{A.ptr.data(), A.idx.data(), A.val.data()};
-    for (int W : {1, 8, 16, 32, 64}) {
-        std::vector<double> work((size_t)khfsai::row_doubles((int)qmax, cplx), -3.0), got((size_t)P.nnz() * w + 1, -7.0), dgot((size_t)A.n + 1, -7.0);
-        const int64_t bad = khfsai::build_host(A.n, csr, P.ptr.data(), P.idx.data(), (int)qmax, W, cplx, work.data(), got.data(), dgot.data());
-        const bool same = memcmp(got.data(), want.data(), sizeof(double) * got.size()) == 0 &&
-                          memcmp(dgot.data(), dwant.data(), sizeof(double) * dgot.size()) == 0 && bad == bad_want;
-        printf("%s/%s/%d q=%lld bad=%lld bits=%s\n", name, cplx ? "z" : "r", W, (long long)qmax, (long long)bad, same ? "ok" : "DIFFER");
-        if (!same) failures += 1;
-    }
-}
-
-void both(const char* name, const Mat& A, const Mat& P) {
-    run_case(name, A, P, false);
-    run_case(name, make_hermitian(A), P, true);
-}
-
-void refused(const char* name, const Mat& A, const Mat& P, int64_t n_override = -1, int64_t nnz_override = -1) {
-    int64_t qmax = 0;
-    const std::string why = khfsai::validate(n_override >= 0 ? n_override : A.n, nnz_override >= 0 ? nnz_override : A.nnz(), A.ptr.data(),
-                                             A.idx.data(), P.nnz(), P.ptr.data(), P.idx.data(), &qmax);
-    printf("%s %s: %s\n", name, why.empty() ? "ACCEPTED" : "refused", why.c_str());
-    if (why.empty()) failures += 1;
+    return khfsai::build_host(A.n, csr, P.ptr.data(), P.idx.data(), qmax, W, cplx, work, got[0].data(), got[1].data());
 }
 
 }  // namespace
 
 int main() {
+    lcg_state = 4321;
     const Mat A = laplacian(13, 9, 0.0);
     const Mat A2 = pattern_product(A, A), A3 = pattern_product(A2, A), A4 = pattern_product(A3, A);
     both("grid_tril_A", A, lower(A));            // q <= 3
@@ -283,35 +201,9 @@ int main() {
     both("indefinite", laplacian(9, 7, 3.0), lower(laplacian(9, 7, 3.0)));          // row 1: d = 1 - (-1 / 1) * (-1) = 0 exactly
     // every validation error
     const Mat LA = lower(A);
-    refused("n_zero", A, LA, 0);
-    refused("n_too_large", A, LA, (int64_t)1 << 31);
-    refused("nnz_too_large", A, LA, -1, (int64_t)1 << 31);
+    refused_inputs(A, LA, 15, 16);
     {
-        Mat U = A;
-        std::swap(U.idx[(size_t)U.ptr[5]], U.idx[(size_t)U.ptr[5] + 1]);
-        refused("unsorted_A", U, LA);
-        Mat Up = LA;
-        std::swap(Up.idx[(size_t)Up.ptr[15]], Up.idx[(size_t)Up.ptr[15] + 1]);
-        refused("unsorted_pattern", A, Up);
-        Mat Dp = A;
-        Dp.idx[(size_t)Dp.ptr[6] + 1] = Dp.idx[(size_t)Dp.ptr[6]];
-        refused("duplicate_A", Dp, LA);
-        Mat Dq = LA;
-        Dq.idx[(size_t)Dq.ptr[16] + 1] = Dq.idx[(size_t)Dq.ptr[16]];
-        refused("duplicate_pattern", A, Dq);
-        Mat O = A;
-        O.idx[(size_t)O.ptr[8] - 1] = (int32_t)A.n;
-        refused("out_of_range_A", O, LA);
-        Mat Op = LA;
-        Op.idx[(size_t)Op.ptr[8] - 1] = (int32_t)A.n;
-        refused("out_of_range_pattern", A, Op);
-        Mat N = A;
-        N.idx[(size_t)N.ptr[2]] = -1;
-        refused("negative_column", N, LA);
-        Mat Q = A;
-        Q.ptr[3] = Q.ptr[2] - 1;
-        refused("indptr_not_ascending", Q, LA);
-        refused("upper_entries", A, A);                          // the full pattern of A: row 0 ends in column 9
+        refused("upper_entries", A, A);                         // the full pattern of A: row 0 ends in column 9
         Triplets t;
         for (int32_t i = 0; i < A.n; ++i)
             for (int32_t p = LA.ptr[(size_t)i]; p < LA.ptr[(size_t)i + 1]; ++p)

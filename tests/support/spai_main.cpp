@@ -1,52 +1,20 @@
 // Stand-alone host program around krypy_amd/csrc/spai.h - TEST INFRASTRUCTURE ONLY (tests/test_spai_host.py compiles it with
 // -fsanitize=address,undefined and runs it as a child process).  For every case, real and complex, it computes all rows
-//   - with plain_row() below: the contract as ONE sequential loop, written here without the header's phases, and
+//   - with plain_row_r / plain_row_z below: the contract as ONE sequential loop, written here without the header's phases, and
 //   - with khspai::build_host() on W = 1 / 8 / 16 / 32 / 64 emulated lanes, the split the kernel makes,
 // and compares the bits (memcmp: a NaN must be the very same NaN).  One line per case and W:
 //   <case>/<r|z>/<W> q=<longest pattern row> bad=<first broken row> bits=<ok|DIFFER>
 // then one line per refused input:  <name> refused: <message>.  Exit status 1 when any bits differ.
-#include <stdio.h>
-#include <string.h>
-
-#include <algorithm>
-#include <string>
-#include <vector>
-
+// The cases' matrices and the comparison are in sai_main.h, shared with fsai_main.cpp.
 #include "spai.h"
+
+#include "sai_main.h"
 
 namespace {
 
-struct Mat {
-    int64_t n = 0;
-    std::vector<int32_t> ptr, idx;
-    std::vector<double> val;      // real: one per entry; complex: pairs
-    int64_t nnz() const { return (int64_t)idx.size(); }
-};
-
-uint64_t lcg_state = 12345;
-double lcg() {      // uniform in (-1, 1), deterministic
-    lcg_state = lcg_state * 6364136223846793005ull + 1442695040888963407ull;
-    return (double)((lcg_state >> 11) & ((1ull << 53) - 1)) / (double)(1ull << 52) - 1.0;
-}
-
-// entries (row, col, value) -> CSR, sorted (the entries are unique)
-Mat from_triplets(int64_t n, std::vector<std::pair<std::pair<int32_t, int32_t>, double>> t) {
-    std::sort(t.begin(), t.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
-    Mat m;
-    m.n = n;
-    m.ptr.assign((size_t)n + 1, 0);
-    for (const auto& e : t) {
-        m.ptr[(size_t)e.first.first + 1] += 1;
-        m.idx.push_back(e.first.second);
-        m.val.push_back(e.second);
-    }
-    for (int64_t i = 0; i < n; ++i) m.ptr[(size_t)i + 1] += m.ptr[(size_t)i];
-    return m;
-}
-
 // five-point Laplacian with upwind convection inside a grid line
 Mat convection(int nx, int ny, double wind) {
-    std::vector<std::pair<std::pair<int32_t, int32_t>, double>> t;
+    Triplets t;
     for (int ix = 0; ix < nx; ++ix)
         for (int iy = 0; iy < ny; ++iy) {
             const int32_t i = ix * ny + iy;
@@ -61,29 +29,13 @@ Mat convection(int nx, int ny, double wind) {
 
 // a band of half-width hw with seeded values and a dominant diagonal
 Mat band(int n, int hw) {
-    std::vector<std::pair<std::pair<int32_t, int32_t>, double>> t;
+    Triplets t;
     for (int i = 0; i < n; ++i)
         for (int j = std::max(0, i - hw); j <= std::min(n - 1, i + hw); ++j) t.push_back({{i, j}, i == j ? 2.0 * hw + 1.0 + lcg() : lcg()});
     return from_triplets(n, t);
 }
 
-// the pattern of A * B (values 1)
-Mat pattern_product(const Mat& A, const Mat& B) {
-    std::vector<std::pair<std::pair<int32_t, int32_t>, double>> t;
-    for (int32_t i = 0; i < A.n; ++i) {
-        std::vector<int32_t> cols;
-        for (int32_t p = A.ptr[(size_t)i]; p < A.ptr[(size_t)i + 1]; ++p) {
-            const int32_t k = A.idx[(size_t)p];
-            cols.insert(cols.end(), B.idx.begin() + B.ptr[(size_t)k], B.idx.begin() + B.ptr[(size_t)k + 1]);
-        }
-        std::sort(cols.begin(), cols.end());
-        cols.erase(std::unique(cols.begin(), cols.end()), cols.end());
-        for (int32_t c : cols) t.push_back({{i, c}, 1.0});
-    }
-    return from_triplets(A.n, t);
-}
-
-Mat make_complex(const Mat& A) {
+Mat complex_case(const Mat& A) {
     Mat Z = A;
     Z.val.resize(2 * A.val.size());
     for (size_t p = 0; p < A.val.size(); ++p) {
@@ -92,13 +44,6 @@ Mat make_complex(const Mat& A) {
     }
     return Z;
 }
-
-struct C {
-    double r, i;
-};
-C mul(C a, C b) { return {a.r * b.r - a.i * b.i, a.r * b.i + a.i * b.r}; }
-C cj(C a) { return {a.r, -a.i}; }
-C sub(C a, C b) { return {a.r - b.r, a.i - b.i}; }
 
 // The contract, complex form, one sequential loop.  For real data every imaginary part is +0 or -0 and no real part depends on
 // one: x - (+-0 * +-0) may turn a -0 real part into +0, so the real form is spelled out separately below.
@@ -147,8 +92,8 @@ bool plain_row_z(const Mat& A, const int32_t* J, int q, int32_t i, double* m) {
         C s{y[(size_t)a].r / d[(size_t)a], y[(size_t)a].i / d[(size_t)a]};
         for (int k = a + 1; k < q; ++k) s = sub(s, mul(cj(L[(size_t)k * q + a]), mm[(size_t)k]));
         mm[(size_t)a] = s;
-        m[2 * a] = s.r != s.r ? __builtin_nan("") : s.r;          // a NaN is stored as 0x7ff8000000000000
-        m[2 * a + 1] = s.i != s.i ? __builtin_nan("") : s.i;
+        m[2 * a] = canon(s.r);
+        m[2 * a + 1] = canon(s.i);
     }
     return bad;
 }
@@ -194,57 +139,31 @@ bool plain_row_r(const Mat& A, const int32_t* J, int q, int32_t i, double* m) {
     for (int a = q - 1; a >= 0; --a) {
         double s = y[(size_t)a] / d[(size_t)a];
         for (int k = a + 1; k < q; ++k) s = s - L[(size_t)k * q + a] * m[k];
-        m[a] = s != s ? __builtin_nan("") : s;          // a NaN is stored as 0x7ff8000000000000
+        m[a] = canon(s);
     }
     return bad;
 }
 
-int failures = 0;
+// ---- the hooks of sai_main.h ----------------------------------------------------------------------------------------------
+std::string validate(int64_t n, int64_t nnz, const Mat& A, const Mat& P, int64_t* qmax) {
+    return khspai::validate(n, nnz, A.ptr.data(), A.idx.data(), P.nnz(), P.ptr.data(), P.idx.data(), qmax);
+}
 
-void run_case(const char* name, const Mat& A, const Mat& P, bool cplx) {
-    int64_t qmax = 0;
-    const std::string why = khspai::validate(A.n, A.nnz(), A.ptr.data(), A.idx.data(), P.nnz(), P.ptr.data(), P.idx.data(), &qmax);
-    if (!why.empty()) {
-        printf("%s/%s refused: %s\n", name, cplx ? "z" : "r", why.c_str());
-        failures += 1;
-        return;
-    }
-    const int w = cplx ? 2 : 1;
-    std::vector<double> want((size_t)P.nnz() * w + 1, -7.0);
-    int64_t bad_want = -1;
-    for (int64_t i = 0; i < A.n; ++i) {
-        const int32_t p0 = P.ptr[(size_t)i];
-        const int q = P.ptr[(size_t)i + 1] - p0;
-        const bool b = cplx ? plain_row_z(A, P.idx.data() + p0, q, (int32_t)i, want.data() + 2 * (size_t)p0)
-                            : plain_row_r(A, P.idx.data() + p0, q, (int32_t)i, want.data() + p0);
-        if (b && bad_want < 0) bad_want = i;
-    }
+Outputs blank_outputs(const Mat&, const Mat& P, bool cplx) { return {std::vector<double>((size_t)P.nnz() * (cplx ? 2 : 1) + 1, -7.0)}; }
+
+bool plain_row(const Mat& A, const int32_t* J, int q, int64_t i, int32_t p0, bool cplx, Outputs& want) {
+    return cplx ? plain_row_z(A, J, q, (int32_t)i, want[0].data() + 2 * (size_t)p0) : plain_row_r(A, J, q, (int32_t)i, want[0].data() + p0);
+}
+
+int64_t lanes_build(const Mat& A, const Mat& P, int qmax, int W, bool cplx, double* work, Outputs& got) {
     const khspai::Csr csr{A.ptr.data(), A.idx.data(), A.val.data()};
-    for (int W : {1, 8, 16, 32, 64}) {
-        std::vector<double> work((size_t)khspai::row_doubles((int)qmax, cplx), -3.0), got((size_t)P.nnz() * w + 1, -7.0);
-        const int64_t bad = khspai::build_host(A.n, csr, P.ptr.data(), P.idx.data(), (int)qmax, W, cplx, work.data(), got.data());
-        const bool same = memcmp(got.data(), want.data(), sizeof(double) * got.size()) == 0 && bad == bad_want;
-        printf("%s/%s/%d q=%lld bad=%lld bits=%s\n", name, cplx ? "z" : "r", W, (long long)qmax, (long long)bad, same ? "ok" : "DIFFER");
-        if (!same) failures += 1;
-    }
-}
-
-void both(const char* name, const Mat& A, const Mat& P) {
-    run_case(name, A, P, false);
-    run_case(name, make_complex(A), P, true);
-}
-
-void refused(const char* name, const Mat& A, const Mat& P, int64_t n_override = -1, int64_t nnz_override = -1) {
-    int64_t qmax = 0;
-    const std::string why = khspai::validate(n_override >= 0 ? n_override : A.n, nnz_override >= 0 ? nnz_override : A.nnz(), A.ptr.data(),
-                                             A.idx.data(), P.nnz(), P.ptr.data(), P.idx.data(), &qmax);
-    printf("%s %s: %s\n", name, why.empty() ? "ACCEPTED" : "refused", why.c_str());
-    if (why.empty()) failures += 1;
+    return khspai::build_host(A.n, csr, P.ptr.data(), P.idx.data(), qmax, W, cplx, work, got[0].data());
 }
 
 }  // namespace
 
 int main() {
+    lcg_state = 12345;
     const Mat A = convection(13, 9, 0.4);
     both("grid_pattern_A", A, A);                              // q <= 5
     both("grid_pattern_A2", A, pattern_product(A, A));        // q <= 13
@@ -252,7 +171,7 @@ int main() {
     both("band_q31", B, band(70, 15));                         // q up to 31: the 32-lane kernel's range, rows of 16 .. 31
     both("band_q32", band(40, 16), [] {                        // one row of exactly 32 entries among short ones
         Mat P = band(40, 1);
-        std::vector<std::pair<std::pair<int32_t, int32_t>, double>> t;
+        Triplets t;
         for (int32_t i = 0; i < 40; ++i)
             for (int32_t p = P.ptr[(size_t)i]; p < P.ptr[(size_t)i + 1]; ++p)
                 if (i != 20) t.push_back({{i, P.idx[(size_t)p]}, 1.0});
@@ -261,7 +180,7 @@ int main() {
     }());
     {   // an empty pattern row, and a pattern without the diagonal
         Mat P = A;
-        std::vector<std::pair<std::pair<int32_t, int32_t>, double>> t;
+        Triplets t;
         for (int32_t i = 0; i < A.n; ++i)
             for (int32_t p = A.ptr[(size_t)i]; p < A.ptr[(size_t)i + 1]; ++p)
                 if (i != 7 && A.idx[(size_t)p] != i) t.push_back({{i, A.idx[(size_t)p]}, 1.0});
@@ -270,7 +189,7 @@ int main() {
     {   // breakdowns, exact by construction: rows 3 and 4 of A identical (d = 0 exactly for every pattern row that holds both), row 9 zero
         Mat D = band(12, 1);
         for (int32_t p = D.ptr[4]; p < D.ptr[5]; ++p) D.val[(size_t)p] = 0.0;
-        std::vector<std::pair<std::pair<int32_t, int32_t>, double>> t;
+        Triplets t;
         for (int32_t i = 0; i < 12; ++i)
             for (int32_t p = D.ptr[(size_t)i]; p < D.ptr[(size_t)i + 1]; ++p)
                 if (i != 3 && i != 4) t.push_back({{i, D.idx[(size_t)p]}, i == 9 ? 0.0 : D.val[(size_t)p]});
@@ -278,30 +197,7 @@ int main() {
             for (int32_t c = 2; c <= 5; ++c) t.push_back({{i, c}, 1.0 + 0.25 * c});
         both("breakdown", from_triplets(12, t), D);
     }
-    // every validation error
-    refused("n_zero", A, A, 0);
-    refused("n_too_large", A, A, (int64_t)1 << 31);
-    refused("nnz_too_large", A, A, -1, (int64_t)1 << 31);
-    {
-        Mat U = A;
-        std::swap(U.idx[(size_t)U.ptr[5]], U.idx[(size_t)U.ptr[5] + 1]);
-        refused("unsorted_A", U, A);
-        refused("unsorted_pattern", A, U);
-        Mat Dp = A;
-        Dp.idx[(size_t)Dp.ptr[6] + 1] = Dp.idx[(size_t)Dp.ptr[6]];
-        refused("duplicate_A", Dp, A);
-        refused("duplicate_pattern", A, Dp);
-        Mat O = A;
-        O.idx[(size_t)O.ptr[8] - 1] = (int32_t)A.n;
-        refused("out_of_range_A", O, A);
-        refused("out_of_range_pattern", A, O);
-        Mat N = A;
-        N.idx[(size_t)N.ptr[2]] = -1;
-        refused("negative_column", N, A);
-        Mat Q = A;
-        Q.ptr[3] = Q.ptr[2] - 1;
-        refused("indptr_not_ascending", Q, A);
-    }
+    refused_inputs(A, A, 5, 6);
     refused("q33", band(50, 16), band(50, 16));
     return failures ? 1 : 0;
 }
