@@ -1169,14 +1169,25 @@ __global__ __launch_bounds__(CH_BS) void k_mgs_chain(ChainArgs a) {
 // there.  The update phase also walks the batches in REVERSE order, so the last batch of the dot phase
 // is still in the register ring and is used again without any load.  The parked set is a ROW count
 // (LROWS): at N = 10^7 (R2 = 40, batches of 5 rows) it is 19 rows - three whole batches and four rows
-// of the fourth, all the LDS there is beside smd / smu / slead - so 19 rows from LDS + 5 from the ring
-// = 24 of the 40 rows of the second read stay on the chip and 16 rows (4 MB per XCD, the size of its
-// L2) are read again; the split batch parks rows 15..18 in the dot phase and re-reads row 19 alone.
+// of the fourth, all the LDS there is beside smd / smu / slead.  The dot phase requests nothing of the
+// column behind its last batch, so it ends with the last TWO batches in the ring (NB-2 in ring[0], NB-1
+// in ring[1]): 19 rows from LDS + 10 from the ring = 29 of the 40 rows of the second read stay on the
+// chip and 11 rows (rows 19..29: 2.73 MB per XCD with 31 workgroups, of the 4 MB of its L2) are read
+// again; the split batch parks rows 15..18 in the dot phase and re-reads row 19 alone.
 // For R2 <= 16 the second read disappears altogether.  Only for B == V (no preconditioner).
-// Ring parity: batch NB-1 sits in ring[1]; the NG = NB - 1 - LROWS / PB ring steps that bring rows back
-// from memory start in ring[0] and NG is even, so the next column's first batch lands in ring[0] again
-// (the step of a split batch loads only its rows >= LROWS).
+// Ring: NG = NB - 1 - LROWS / PB batches lie between the parked ones and the last; NG - 1 of them come
+// back from memory, and the ring loads of the update phase are dealt to the slots so that the next
+// column's first batch lands in ring[0] again (see there; the step of a split batch loads only its rows
+// >= LROWS).  No load of the column is in flight across the grid-wide sum.
+// KH_CH_HOLD2 = 0 is the schedule before that one, kept for A/B builds: the dot phase ends with a second
+// request for batch NB-2 into ring[0], in flight across the sum, NG batches (16 rows at R2 = 40, the
+// whole L2) come back from memory, starting in ring[0], and NG must be even for the next column's first
+// batch to land there.
 // ------------------------------------------------------------------------------------------
+#ifndef KH_CH_HOLD2
+#define KH_CH_HOLD2 2     // 1, 2: the two places of the next column's first request among the re-reads (update phase)
+#endif
+static_assert(KH_CH_HOLD2 >= 0 && KH_CH_HOLD2 <= 2, "KH_CH_HOLD2: 0 (the earlier schedule), 1 or 2");
 // (experiment knob: the first KH_CH_REUSE_SKIP of the batches that come back from memory for the update are
 // streamed non-temporally as well, i.e. given up to HBM so that the others fit the 4 MB of L2 per XCD)
 #ifndef KH_CH_REUSE_SKIP
@@ -1184,7 +1195,9 @@ __global__ __launch_bounds__(CH_BS) void k_mgs_chain(ChainArgs a) {
 #endif
 // (experiment knobs, round 2: KH_CH_SKIP_LAST = 1 streams batch NB-2 non-temporally too - its second read is issued
 // BEFORE the grid-wide reduction and hidden by it, so it may come from further away and leave the L2 to the other
-// NG-1 batches; KH_CH_LDS_EARLY = 1 runs the LDS-parked part of the update while the first re-read batches fly)
+// NG-1 batches [with KH_CH_HOLD2 != 0 that batch is not read again at all and the knob gives up batch NB-3];
+// KH_CH_LDS_EARLY = 1 runs the LDS-parked part of the update while the first re-read batches fly [KH_CH_HOLD2 != 0:
+// the two that are requested together right behind the sum])
 #ifndef KH_CH_SKIP_LAST
 #define KH_CH_SKIP_LAST 0
 #endif
@@ -1211,7 +1224,10 @@ struct ChainShapeLds {
     // beside the static arrays, 19 rows = 152 KB (20 would leave no room for smd / smu / slead)
     static constexpr int LROWS = (R2 == 40 && !CPLX) ? 19 : (NB >= 4 ? 3 : 1) * PB;
     static constexpr int NG = NB - 1 - LROWS / PB;            // ring steps of the update that load rows from memory
-    static_assert((NB % 2) == 0 && NG >= 0 && (NG % 2) == 0, "ring parity must reset every phase");
+    static_assert((NB % 2) == 0 && NG >= 0, "the dot phase starts in ring[0] and must end with batch NB-1 in ring[1]");
+    // (NG itself may be odd or even: the update phase deals its NG - 1 re-reads and the next column's batch 0 to the slots by
+    // their place in the order of issue, batch 0 always to ring[0])
+    static_assert(KH_CH_HOLD2 != 0 || (NG % 2) == 0, "KH_CH_HOLD2 = 0: NG ring steps from ring[0] on must end in ring[0]");
     static_assert(WL <= LROWS && LROWS <= R2 - PB, "the prologue's rows of w borrow parked rows; the last batch stays in the ring");
     static constexpr size_t LDS_BYTES = (size_t)LROWS * CH_BS * sizeof(double2);
     // blocks of the prologue's x window (chain_apply_banded_xwin): the parked rows that the prologue's rows of w leave free
@@ -1231,6 +1247,8 @@ __global__ __launch_bounds__(CH_BS) void k_mgs_chain_lds(ChainArgs a) {
     constexpr int LBC = (LROWS + PB - 1) / PB;    // batches with a parked row
     constexpr bool SPLIT = (LROWS % PB) != 0;     // the last of them is parked in part (the row tests below fold away otherwise)
     constexpr int NG = ChainShapeLds<R2, CPLX>::NG;
+    constexpr bool HOLD2 = (KH_CH_HOLD2 != 0) && NG > 0;   // the dot phase ends with batches NB-2 and NB-1 both in the ring
+    constexpr int RLAST = HOLD2 ? NB - 3 : NB - 2;         // the last batch that comes back from memory for the update
     // prologue only: the operator's last WL rows of w wait in LDS (the FND = 0 prologue loads straight into registers)
     constexpr int WL = FND > 0 ? ChainShapeLds<R2, CPLX>::WL : 0;
     constexpr int RW = R2 - WL;                   // rows of w the prologue holds in registers
@@ -1335,13 +1353,15 @@ __global__ __launch_bounds__(CH_BS) void k_mgs_chain_lds(ChainArgs a) {
         for (int b = 0; b < NB; ++b) {
             // next: v_j batch b+1; after the last one the first update batch that is not in LDS (of a split batch
             // only the rows that are not) or, if the whole column is, the next column's first batch
+            // (HOLD2: nothing after the last one - ring[0] keeps batch NB-2, which is therefore streamed like the last batch)
             const double2* __restrict__ nx = (b + 1 < NB) ? v2 + (int64_t)(b + 1) * PB * CH_BS
                                                             : (NG > 0 ? v2 + (int64_t)(NB - 2) * PB * CH_BS : vn);
 #pragma unroll
             for (int i = 0; i < PB; ++i) {
+                if (HOLD2 && b + 1 == NB) continue;
                 if (!SPLIT || b + 1 < NB || NG == 0 || (NB - 2) * PB + i >= LROWS)
                     ring[(b + 1) & 1][i] = CH_LD(nx + (int64_t)i * CH_BS, (b + 1 < NB) && (!SPLIT || (b + 1) * PB + i >= LROWS) &&
-                                                                              (b + 1 >= LROWS / PB + KH_CH_REUSE_SKIP) && (b + 1 <= NB - 2 - KH_CH_SKIP_LAST));
+                                                                              (b + 1 >= LROWS / PB + KH_CH_REUSE_SKIP) && (b + 1 <= RLAST - KH_CH_SKIP_LAST));
             }
             CH_ISSUE_FENCE();
 #pragma unroll
@@ -1403,6 +1423,71 @@ __global__ __launch_bounds__(CH_BS) void k_mgs_chain_lds(ChainArgs a) {
         }                                                         \
         W_PUT(r, wr_);                                            \
     } while (0)
+        // the parked head of the column from LDS (own entries: no barrier needed), one batch of reads at a time (hoisted all
+        // together they would spill)
+#define CH_UPD_HEAD()                                                         \
+    do {                                                                      \
+        _Pragma("unroll") for (int bb = LBC - 1; bb >= 0; --bb) {             \
+            CH_ISSUE_FENCE();                                                 \
+            _Pragma("unroll") for (int i = 0; i < PB; ++i) {                  \
+                if (!SPLIT || bb * PB + i < LROWS) {                          \
+                    const double2 p = vlds[(bb * PB + i) * CH_BS + tid];      \
+                    CH_UPD(bb * PB + i, p);                                   \
+                }                                                             \
+            }                                                                 \
+        }                                                                     \
+        CH_ISSUE_FENCE();                                                     \
+    } while (0)
+        if constexpr (HOLD2) {
+            // (a) the last TWO batches of the dot phase are still in the ring: NB-1 in ring[1], NB-2 in ring[0]
+#pragma unroll
+            for (int i = 0; i < PB; ++i) CH_UPD((NB - 1) * PB + i, ring[1][i]);
+#pragma unroll
+            for (int i = 0; i < PB; ++i) CH_UPD((NB - 2) * PB + i, ring[0][i]);
+            // (b) rows (NB-2)*PB - 1 ... LROWS from memory: MS steps, a batch each (the last one may be a part of one).  With the
+            //     next column's batch 0 that is MS + 1 ring loads, numbered p = 0 ... MS in the order of their issue; batch 0 is
+            //     load VP and step s load s + (s >= VP).  Load p goes to ring[(p + VP) & 1]: batch 0 to ring[0] whatever MS is,
+            //     its neighbours to ring[1], and load p + 2 to the slot that load p's update has just freed.  Both slots are
+            //     free here, so loads 0 and 1 leave together: one exposed L2 round trip.
+            //     KH_CH_HOLD2 = 1: batch 0 takes the place of the last step but one (requested as early as the ring allows);
+            //     2: it is requested last, so that no re-read of this column waits behind a miss to HBM.
+            constexpr int MS = NG - 1;
+            constexpr int VP = (KH_CH_HOLD2 == 2 || MS == 0) ? MS : MS - 1;
+#define CH_H2_ISSUE(p_)                                                                                                   \
+    do {                                                                                                                  \
+        if ((p_) == VP) {                                                                                                 \
+            _Pragma("unroll") for (int i = 0; i < PB; ++i) ring[0][i] = CH_LD(vn + (int64_t)i * CH_BS, false);            \
+        } else {                                                                                                          \
+            const int bq_ = NB - 3 - ((p_) < VP ? (p_) : (p_) - 1);                                                       \
+            _Pragma("unroll") for (int i = 0; i < PB; ++i) {                                                              \
+                if (!SPLIT || bq_ * PB + i >= LROWS)                                                                      \
+                    ring[((p_) + VP) & 1][i] = CH_LD(v2 + (int64_t)(bq_ * PB + i) * CH_BS, false);                        \
+            }                                                                                                             \
+        }                                                                                                                 \
+        CH_ISSUE_FENCE();                                                                                                 \
+    } while (0)
+            CH_H2_ISSUE(0);
+            if (MS >= 1) CH_H2_ISSUE(1);
+            // (KH_CH_LDS_EARLY = 1: the parked head while those two fly)
+            if (KH_CH_LDS_EARLY != 0) CH_UPD_HEAD();
+#pragma unroll
+            for (int s = 0; s < MS; ++s) {
+                const int p = s < VP ? s : s + 1;
+                const int b = NB - 3 - s;
+#pragma unroll
+                for (int i = 0; i < PB; ++i) {
+                    if (!SPLIT || b * PB + i >= LROWS) CH_UPD(b * PB + i, ring[(p + VP) & 1][i]);
+                }
+                if (p + 2 <= MS) CH_H2_ISSUE(p + 2);
+            }
+#undef CH_H2_ISSUE
+            CH_STAMP(a, t, total, 6);
+            // (c) the head of the column from LDS
+            if (KH_CH_LDS_EARLY == 0) CH_UPD_HEAD();
+        } else {
+        // KH_CH_HOLD2 = 0, or NG == 0 (nothing comes back from memory).  Left word for word - its own copies of the LDS-head
+        // loop and its indentation included - as it was before the schedule above: an A/B build must run the earlier code
+        // exactly, and the fences of CH_UPD_HEAD sit one place differently.
         // (a) the last batch of the dot phase is still in ring[1]
 #pragma unroll
         for (int i = 0; i < PB; ++i) CH_UPD((NB - 1) * PB + i, ring[1][i]);
@@ -1453,6 +1538,8 @@ __global__ __launch_bounds__(CH_BS) void k_mgs_chain_lds(ChainArgs a) {
                 }
             }
         }
+        }          // (the schedule of KH_CH_HOLD2 = 0)
+#undef CH_UPD_HEAD
 #undef CH_UPD
         CH_STAMP(a, t, total, 7);
     }
