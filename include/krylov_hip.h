@@ -399,6 +399,42 @@ int kh_cg_cycle(kh_ctx ctx, kh_mat A, kh_mat Md, kh_vec Pd, int64_t pcol, kh_vec
                 kh_vec R, int64_t rcol, kh_vec Z, int64_t zcol, int64_t k0, int64_t k_stop, double tol, double bnorm,
                 double* rhos, double* trace, int64_t* k_done, int* reason);
 
+/* ---- BiCGStab (real fp64; krypy_amd/csrc/bicgstab.hip) ------------------------------------ */
+/* One iteration on the operator A^ = Ml A Mr, every elementwise expression rounded as written (r~ fixed for the solve):
+ *   k > 0:  p = r + beta * (p - omega * v)
+ *           v = A^ p ;  sigma = <r~, v> ;  alpha = rho / sigma          (formed on the device)
+ *           s = r - alpha * v ;  ss = <s, s>
+ *           t = A^ s ;  theta = <t, s> ;  phi = <t, t> ;  omega = theta / phi   (on the device)
+ *           y = (y + alpha * p) + omega * s ;  r = s - omega * t ;  rho' = <r~, r> ;  rr = <r, r>
+ * An alpha or omega that is not finite is clamped to 0 on the device: no vector receives inf / nan from finite input.  The
+ * sums have a fixed order (no atomics) and are all-reduced over the ranks where they are formed.  All vectors are columns of
+ * real device blocks of one length; a column that is written must differ from every column read (KH_ERR_ARG otherwise).
+ * Sanity word beside the sums (0 = fine): */
+#define KH_BICG_NONFINITE_SIGMA 1  /* <r~, v> is inf / nan */
+#define KH_BICG_ALPHA_CLAMPED 2    /* rho and <r~, v> are finite but rho / <r~, v> is not (a zero divisor): the device took alpha = 0 */
+#define KH_BICG_OMEGA_CLAMPED 4    /* <t, s> / <t, t> is not finite (t = 0 when s = 0: the regular early end): the device took omega = 0 */
+#define KH_BICG_RHO_ZERO 8         /* <r~, r> of the new residual is 0 or not finite: the next beta cannot be formed */
+/* p = r + beta * (p - omega * v) */
+int kh_bicgstab_dir(kh_ctx ctx, kh_vec R, int64_t rcol, kh_vec P, int64_t pcol, kh_vec V, int64_t vcol, double beta,
+                    double omega);
+/* sigma = <r~, v>; alpha = rho / sigma (kept on the device for kh_bicgstab_full); s = r - alpha v.
+ * out[0] = sigma, out[1] = <s, s>, out[2] = sanity word (NONFINITE_SIGMA, ALPHA_CLAMPED).  One host synchronisation. */
+int kh_bicgstab_half(kh_ctx ctx, kh_vec RT, int64_t rtcol, kh_vec R, int64_t rcol, kh_vec V, int64_t vcol, kh_vec S,
+                     int64_t scol, double rho, double* out);
+/* theta = <t, s>, phi = <t, t>; omega = theta / phi; y = (y + alpha p) + omega s; r = s - omega t, with the alpha of the
+ * kh_bicgstab_half call before it.  theta_known = 1: <t, s> already lies, complete, in the context's scratch scalar for it
+ * (left there by an SpMV epilogue) and only phi is summed.  out[0] = theta, out[1] = phi, out[2] = rho', out[3] = rr,
+ * out[4] = sanity word (OMEGA_CLAMPED, RHO_ZERO).  One host synchronisation. */
+int kh_bicgstab_full(kh_ctx ctx, kh_vec RT, int64_t rtcol, kh_vec R, int64_t rcol, kh_vec P, int64_t pcol, kh_vec S,
+                     int64_t scol, kh_vec T, int64_t tcol, kh_vec YK, int64_t ycol, int theta_known, double* out);
+/* The whole iteration in one call and ONE host synchronisation (A real: CSR, dense or diagonal): the direction update
+ * (skipped when `first`; beta, omega_prev are the host's), both applications of A, the two halves above.  rho = <r~, r>.
+ * out[0..5] = sigma, ss, theta, phi, rho', rr; out[6] = sanity word; out[7] = 0 (reserved).  The same bits as
+ * kh_bicgstab_dir, kh_apply, kh_bicgstab_half, kh_apply, kh_bicgstab_full(theta_known = 0) in a row. */
+int kh_bicgstab_step(kh_ctx ctx, kh_mat A, kh_vec RT, int64_t rtcol, kh_vec R, int64_t rcol, kh_vec P, int64_t pcol, kh_vec V,
+                     int64_t vcol, kh_vec S, int64_t scol, kh_vec T, int64_t tcol, kh_vec YK, int64_t ycol, int first,
+                     double beta, double omega_prev, double rho, double* out);
+
 /* ---- complex (c128) twin of the hot path ------------------------------------------------- */
 /* KryPy's kernels are dtype-generic NumPy (H/V are allocated with the common dtype of A, v, M:
  * utils.py:893-905, complex inner products are X^H Y: utils.py:183).  A complex N-vector block is

@@ -32,6 +32,8 @@ _INT = ctypes.c_int
 # sanity word of the fused CG step (KH_CG_* of include/krylov_hip.h)
 CG_NONFINITE_PAP, CG_NONPOSITIVE_PAP, CG_NONFINITE_RHO, CG_NEGATIVE_RHO = 1, 2, 4, 8
 CG_STEP_CLAMPED = 16
+# sanity word of the BiCGStab entries (KH_BICG_* of the header)
+BICG_NONFINITE_SIGMA, BICG_ALPHA_CLAMPED, BICG_OMEGA_CLAMPED, BICG_RHO_ZERO = 1, 2, 4, 8
 # stop reasons of kh_gmres_cycle (KH_CYCLE_* of the header)
 CYCLE_LIMIT, CYCLE_TOL, CYCLE_CHECK = 0, 1, 2
 
@@ -150,6 +152,11 @@ _SIGNATURES = {
                    _c_double_p],
     "kh_cg_cycle": [_H, _H, _H, _H, _I64, _H, _I64, _H, _I64, _H, _I64, _H, _I64, _I64, _I64, _D, _D, _c_double_p,
                     _c_double_p, _c_int64_p, ctypes.POINTER(ctypes.c_int)],
+    "kh_bicgstab_dir": [_H, _H, _I64, _H, _I64, _H, _I64, _D, _D],
+    "kh_bicgstab_half": [_H, _H, _I64, _H, _I64, _H, _I64, _H, _I64, _D, _c_double_p],
+    "kh_bicgstab_full": [_H, _H, _I64, _H, _I64, _H, _I64, _H, _I64, _H, _I64, _H, _I64, _INT, _c_double_p],
+    "kh_bicgstab_step": [_H, _H, _H, _I64, _H, _I64, _H, _I64, _H, _I64, _H, _I64, _H, _I64, _H, _I64, _INT, _D, _D, _D,
+                         _c_double_p],
     "kh_bench_kernel": [_H, _INT, _H, _H, _INT, _c_double_p],
     "kh_bench_arnoldi": [_H, _H, _H, _H, _I64, _INT, _INT, _c_double_p],
     # complex (c128) side: vectors are real blocks of length 2N (interleaved re, im)
@@ -1279,6 +1286,48 @@ class Context(object):
             apcol, YK.handle, ycol, R.handle, rcol, Z.handle if Z is not None else None, zcol,
             1 if first else 0, omega, rho, _dptr(out)), "kh_cg_step")
         return float(out[0]), float(out[1]), float(out[0]), int(out[2])
+
+    # ---- BiCGStab (real fp64; the header has the iteration) ----
+    def bicgstab_dir(self, R, rcol, P, pcol, V, vcol, beta, omega):
+        """``p = r + beta * (p - omega * v)`` in one pass (``kh_bicgstab_dir``)."""
+        if _same_dtype("bicgstab_dir", R, P, V):
+            raise BackendError("bicgstab_dir: real blocks expected")
+        _check(self._lib, self._lib.kh_bicgstab_dir(self._h, R.handle, rcol, P.handle, pcol, V.handle, vcol, float(beta),
+                                                    float(omega)), "kh_bicgstab_dir")
+
+    def bicgstab_half(self, RT, rtcol, R, rcol, V, vcol, S, scol, rho):
+        """``sigma = <rt, v>``; ``alpha = rho / sigma`` (formed and kept on the device); ``s = r - alpha v``.  Returns
+        ``(sigma, <s, s>, flags)`` (``flags``: ``BICG_*``)."""
+        if _same_dtype("bicgstab_half", RT, R, V, S):
+            raise BackendError("bicgstab_half: real blocks expected")
+        out = numpy.empty(3, dtype=numpy.float64)
+        _check(self._lib, self._lib.kh_bicgstab_half(self._h, RT.handle, rtcol, R.handle, rcol, V.handle, vcol, S.handle, scol,
+                                                     float(rho), _dptr(out)), "kh_bicgstab_half")
+        return float(out[0]), float(out[1]), int(out[2])
+
+    def bicgstab_full(self, RT, rtcol, R, rcol, P, pcol, S, scol, T, tcol, YK, ycol, theta_known=False):
+        """``omega = <t, s> / <t, t>`` (on the device); ``y = (y + alpha p) + omega s``; ``r = s - omega t`` with the
+        ``alpha`` of the ``bicgstab_half`` call before it.  Returns ``(theta, phi, rho_new, rr, flags)``."""
+        if _same_dtype("bicgstab_full", RT, R, P, S, T, YK):
+            raise BackendError("bicgstab_full: real blocks expected")
+        out = numpy.empty(5, dtype=numpy.float64)
+        _check(self._lib, self._lib.kh_bicgstab_full(
+            self._h, RT.handle, rtcol, R.handle, rcol, P.handle, pcol, S.handle, scol, T.handle, tcol, YK.handle, ycol,
+            1 if theta_known else 0, _dptr(out)), "kh_bicgstab_full")
+        return float(out[0]), float(out[1]), float(out[2]), float(out[3]), int(out[4])
+
+    def bicgstab_step(self, A, RT, rtcol, R, rcol, P, pcol, V, vcol, S, scol, T, tcol, YK, ycol, first, beta, omega_prev,
+                      rho):
+        """One whole BiCGStab iteration in one call and one host synchronisation (``kh_bicgstab_step``).  Returns
+        ``(sigma, ss, theta, phi, rho_new, rr, flags)``."""
+        if _same_dtype("bicgstab_step", RT, R, P, V, S, T, YK):
+            raise BackendError("bicgstab_step: real blocks expected")
+        out = numpy.empty(8, dtype=numpy.float64)
+        _check(self._lib, self._lib.kh_bicgstab_step(
+            self._h, A.handle, RT.handle, rtcol, R.handle, rcol, P.handle, pcol, V.handle, vcol, S.handle, scol, T.handle,
+            tcol, YK.handle, ycol, 1 if first else 0, float(beta), float(omega_prev), float(rho), _dptr(out)),
+            "kh_bicgstab_step")
+        return tuple(float(x) for x in out[:6]) + (int(out[6]),)
 
     def bench_kernel(self, which, V, W, reps):
         ms = _D(0.0)

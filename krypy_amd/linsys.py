@@ -6,6 +6,7 @@ solver object *is* the result.  All N-vectors stay in HBM between iterations; at
 that the reference exposes as ndarrays (``xk``, ``x0``, ``MMlr0``, ``Mlr0``, ``V``, ``P``,
 ``LinearSystem.Mlb`` ...) are downloaded lazily on first access.  The Hessenberg matrix,
 Givens rotations and the small triangular solves stay on the host like in the reference.
+``Bicgstab`` has no counterpart in the reference (same skeleton, same attributes).
 
 Reference lines are cited as ``linsys.py:<line>`` (= ``/root/reference/krypy/linsys.py``).
 """
@@ -20,7 +21,7 @@ from . import _hip, utils
 from .utils import DVec
 
 __all__ = ["LinearSystem", "TimedLinearSystem", "ConvertedTimedLinearSystem", "Cg", "Minres", "Gmres",
-           "RestartedGmres"]
+           "RestartedGmres", "Bicgstab"]
 
 
 class _LazyHost(object):
@@ -615,6 +616,127 @@ class Cg(_KrylovSolver):
         """Number of operations needed for nsteps of CG (linsys.py:698-708)."""
         return {"A": 1 + nsteps, "M": 2 + nsteps, "Ml": 2 + nsteps, "Mr": 1 + nsteps,
                 "ip_B": 2 + 2 * nsteps, "axpy": 2 + 2 * nsteps}
+
+
+class Bicgstab(_KrylovSolver):
+    r"""BiCGStab (van der Vorst 1992) for non-symmetric systems; the reference has no counterpart.
+
+    A short recurrence on the operator :math:`\hat A = M_l A M_r`: seven vectors at any iteration count, two operator
+    applications and no orthogonalisation per iteration (``include/krylov_hip.h`` has the iteration; the order of its
+    operations is fixed).  With a plain device matrix as :math:`\hat A` every iteration is ONE device call and one host
+    synchronisation (``bicgstab_step``); any other operator - a composite with ``Ml`` / ``Mr``, a triangular-solve or
+    ILU(0) operator, a host callable - is applied through its own ``_apply_dev`` with the fused vector kernels in between
+    (two host synchronisations per iteration).  Both paths compute the same sequence.  Real data, Euclidean inner product.
+
+    ``bicgstab_trace`` holds the last 16 iterations' ``(k, rho, sigma, ss, theta, phi, rho_new, rr, flags)``; a breakdown
+    (``<rt, v>`` zero or not finite, ``<rt, r>`` zero) raises :class:`~utils.ConvergenceError` with them.
+    """
+
+    def __init__(self, linear_system, x0=None, tol=1e-5, maxiter=None, explicit_residual=False, store_arnoldi=False):
+        if not isinstance(linear_system, LinearSystem):
+            raise utils.ArgumentError("linear_system is not an instance of LinearSystem")
+        ls = linear_system
+        if not (isinstance(ls.M, utils.IdentityLinearOperator) and isinstance(ls.Minv, utils.IdentityLinearOperator)):
+            raise utils.ArgumentError("Bicgstab: M / Minv change the inner product, which BiCGStab does not use; pass the "
+                                      "preconditioner as Ml (left) or Mr (right) instead")
+        if not (ls.ip_B is None or isinstance(ls.ip_B, utils.IdentityLinearOperator)):
+            raise utils.ArgumentError("Bicgstab: only the Euclidean inner product (ip_B=None) is implemented; use Gmres for "
+                                      "another inner product")
+        if store_arnoldi:
+            raise utils.ArgumentError("Bicgstab: store_arnoldi=True is not available, BiCGStab builds no Arnoldi relation; "
+                                      "use Gmres for V and H")
+        utils._require_real(ls.dtype, "Bicgstab: the linear system (A, b, Ml or Mr)")
+        utils._require_real(getattr(x0, "dtype", numpy.float64), "Bicgstab: x0")
+        super(Bicgstab, self).__init__(ls, x0=x0, tol=tol, maxiter=maxiter, explicit_residual=explicit_residual)
+
+    def __repr__(self):
+        return self._repr("krypy BiCGStab object")
+
+    @staticmethod
+    def _quot(a, b):
+        """``a / b`` as the device forms alpha and omega: IEEE division, 0 when the quotient is not finite"""
+        with numpy.errstate(all="ignore"):
+            q = float(numpy.float64(a) / numpy.float64(b))
+        return q if numpy.isfinite(q) else 0.0
+
+    def _breakdown(self, k, what, yk):
+        self.xk = self._get_xk(yk)
+        return utils.ConvergenceError(
+            "BiCGStab breakdown in iteration %d (%s); last steps (k, rho, sigma, ss, theta, phi, rho_new, rr, flags): %s"
+            % (k, what, list(self.bicgstab_trace)), self)
+
+    def _solve(self):
+        ls = self.linear_system
+        ctx = self._ctx
+        N = ls.N
+        bdt = self._bdt
+        bnorm = ls.MMlb_norm
+        self.bicgstab_trace = trace = collections.deque(maxlen=16)
+
+        yk = DVec(ctx.alloc(N, 1, dtype=bdt))
+        r = _dev_of(self, "Mlr0", ctx).astype(bdt).copy()
+        rt = r.copy()                                    # the shadow residual, fixed for the solve
+        p = r.copy()
+        v, s, t = (DVec(ctx.alloc(N, 1, dtype=bdt, zero=False)) for _ in range(3))
+        self.iter = 0
+        if not (self.resnorms[-1] > self.tol and self.iter < self.maxiter):
+            if not _is_set(self, "xk"):
+                self.xk = self._get_xk(yk)
+            return
+        rho = float(ctx.dot_panel(rt.block, rt.col, 1, r.block, r.col)[0])
+        rho_prev = alpha = omega = 0.0
+
+        # the whole iteration in one device call when the operator is a plain device matrix
+        Amat = self.MlAMr._device_matrix(ctx, bdt)
+        one_call = Amat is not None and hasattr(ctx, "bicgstab_step")
+        cols = (rt.block, rt.col, r.block, r.col, p.block, p.col, v.block, v.col, s.block, s.col, t.block, t.col,
+                yk.block, yk.col)
+        names = ((_hip.BICG_NONFINITE_SIGMA, "<rt, v> is not finite"), (_hip.BICG_ALPHA_CLAMPED, "<rt, v> = 0: alpha clamped"),
+                 (_hip.BICG_RHO_ZERO, "<rt, r> is zero or not finite"))
+
+        while self.resnorms[-1] > self.tol and self.iter < self.maxiter:
+            k = self.iter
+            beta = 0.0
+            if k > 0:
+                with numpy.errstate(all="ignore"):
+                    beta = float((numpy.float64(rho) / numpy.float64(rho_prev)) * (numpy.float64(alpha) / numpy.float64(omega)))
+                if not numpy.isfinite(beta):
+                    # (omega = 0 with a residual that is not small: t = 0 or t orthogonal to s - no direction to go on with)
+                    raise self._breakdown(k, "beta = (rho / rho_prev) * (alpha / omega) is not finite, omega = %r" % omega, yk)
+            if one_call:
+                sigma, ss, theta, phi, rho_new, rr, flags = ctx.bicgstab_step(Amat, *cols, k == 0, beta, omega, rho)
+            else:
+                if k > 0:
+                    ctx.bicgstab_dir(r.block, r.col, p.block, p.col, v.block, v.col, beta, omega)
+                self.MlAMr._apply_dev(p.block, p.col, v.block, v.col, 1)
+                sigma, ss, f0 = ctx.bicgstab_half(rt.block, rt.col, r.block, r.col, v.block, v.col, s.block, s.col, rho)
+                self.MlAMr._apply_dev(s.block, s.col, t.block, t.col, 1)
+                theta, phi, rho_new, rr, f1 = ctx.bicgstab_full(rt.block, rt.col, r.block, r.col, p.block, p.col, s.block, s.col,
+                                                                t.block, t.col, yk.block, yk.col)
+                flags = f0 | f1
+            trace.append((k, rho, sigma, ss, theta, phi, rho_new, rr, flags))
+            alpha = self._quot(rho, sigma)               # the step lengths the device took (same IEEE divisions)
+            omega = self._quot(theta, phi)
+            resnorm = numpy.sqrt(numpy.float64(abs(rr)))
+            bad = [text for bit, text in names if flags & bit]
+            if bad and not resnorm / bnorm <= self.tol:
+                raise self._breakdown(k, "; ".join(bad) + "; flags %d" % flags, yk)
+            try:
+                self._finalize_iteration(yk, resnorm)
+            except utils.ConvergenceError:
+                self.iter += 1                           # the solver an error carries counts the iterations it has done
+                raise
+            rho_prev, rho = rho, rho_new
+            self.iter += 1
+
+        if not _is_set(self, "xk"):      # (reading self.xk would download it)
+            self.xk = self._get_xk(yk)
+
+    @staticmethod
+    def operations(nsteps):
+        """Number of operations needed for nsteps of BiCGStab."""
+        return {"A": 1 + 2 * nsteps, "M": 2, "Ml": 2 + 2 * nsteps, "Mr": 1 + 2 * nsteps,
+                "ip_B": 2 + 5 * nsteps, "axpy": 1 + 6 * nsteps}
 
 
 class _ArnoldiBasisMixin(object):
