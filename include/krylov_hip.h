@@ -435,6 +435,62 @@ int kh_bicgstab_step(kh_ctx ctx, kh_mat A, kh_vec RT, int64_t rtcol, kh_vec R, i
                      int64_t vcol, kh_vec S, int64_t scol, kh_vec T, int64_t tcol, kh_vec YK, int64_t ycol, int first,
                      double beta, double omega_prev, double rho, double* out);
 
+/* ---- IDR(s) with bi-orthogonalisation (real fp64; krypy_amd/csrc/idrs.hip) ----------------- */
+/* van Gijzen & Sonneveld 2011 with ONE block inner product per step (Collignon & van Gijzen 2011) on A^ = Ml A Mr.  Vectors:
+ * the shadow space P, G and U (s columns each, 1 <= s <= KH_IDRS_SMAX; G = U = 0 at the start), r, y, and a scratch column t
+ * that takes every operator product.  One ITERATION is one operator application; a cycle has the positions 0 .. s.  Every
+ * elementwise expression is rounded as written, sums over j and i run in rising order, one term at a time:
+ *   position k < s:  c_i = (f_i - sum_{j=k}^{i-1} M_ij c_j) / M_ii                                   i = k .. s-1
+ *                    v = r ; v = v - c_i g_i ; u_k = om v ; u_k = u_k + c_i u_i  (i = k reads the old u_k)   i = k .. s-1
+ *                    t = A^ u_k ;  h_i = <p_i, t>                                                     i = 0 .. s-1
+ *                    a_i = (h_i - sum_{j<i} M_ij a_j) / M_ii                                          i = 0 .. k-1
+ *                    g_k = t - a_i g_i ;  u_k = u_k - a_i u_i                                         i = 0 .. k-1
+ *                    M_ik = h_i - sum_{j<k} M_ij a_j                                                  i = k .. s-1
+ *                    beta = f_k / M_kk ;  r = r - beta g_k ;  y = y + beta u_k ;  rr = <r, r>
+ *                    f_i = f_i - beta M_ik                                                            i = k+1 .. s-1
+ *   position s:      t = A^ r ;  theta = <t, r> ;  phi = <t, t> ;  om = theta / phi
+ *                    rho = theta / (sqrt(phi) sqrt(rr)) ;  if |rho| < 0.7:  om = (om 0.7) / |rho|
+ *                    y = y + om r ;  r = r - om t ;  rr = <r, r> ;  f_i = <p_i, r>
+ * Every scalar of this lives in the caller's scalar block SC: one zero-initialised column of at least KH_IDRS_NSCAL doubles
+ * (layout: krypy_amd/csrc/idrs.h), and is formed on the device; the host gets one RECORD per step:
+ * (rr, M_kk or theta, f_k or phi, flags).  A quotient that is not finite is clamped to 0 where it is formed: no vector
+ * receives inf / nan from finite input.  After a step with sqrt(rr) / bnorm <= tol, or with a flag, a stop word in SC makes
+ * every IDR kernel queued behind it return at once: P, G, U, r, y and the scalars stand where that step left them (operator
+ * products queued behind it write t only).  Sums have a fixed order (no atomics) and are all-reduced over the ranks where
+ * they are formed.  All columns are pairwise distinct columns of real device blocks of one length (KH_ERR_ARG otherwise). */
+#define KH_IDRS_SMAX 8
+#define KH_IDRS_RUN_MAX 64          /* positions of one kh_idrs_run call at most */
+#define KH_IDRS_NSCAL 361
+#define KH_IDRS_PIVOT_ZERO 1        /* M_kk is zero or not finite where beta or c_k divides by it */
+#define KH_IDRS_OMEGA_CLAMPED 2     /* <t, t> = 0: theta / phi is not finite, the device took 0 */
+#define KH_IDRS_OMEGA_ZERO 4        /* om = 0 after the correction while rr > 0: the next cycle could not move */
+#define KH_IDRS_NONFINITE 8         /* a sum (h, theta, phi, f, rr) is inf / nan */
+/* M = I, om = 1, f = P^T r, rr = <r, r>, stop word, counter and pending flags cleared; *rr_out = rr.  One host
+ * synchronisation.  (G, U and y are the caller's to zero.) */
+int kh_idrs_init(kh_ctx ctx, kh_vec P, int64_t pcol, kh_vec G, int64_t gcol, kh_vec U, int64_t ucol, kh_vec R, int64_t rcol,
+                 kh_vec YK, int64_t ycol, kh_vec T, int64_t tcol, kh_vec SC, int s, double* rr_out);
+/* position k < s up to the operator: c, then u_k.  Clears the stop word and the counter.  The caller then forms t = A^ u_k
+ * (column ucol + k of U into column tcol of T).  Nothing visits the host. */
+int kh_idrs_dir(kh_ctx ctx, kh_vec P, int64_t pcol, kh_vec G, int64_t gcol, kh_vec U, int64_t ucol, kh_vec R, int64_t rcol,
+                kh_vec YK, int64_t ycol, kh_vec T, int64_t tcol, kh_vec SC, int s, int k);
+/* position k < s from the operator product t on: h, a, g_k, u_k, M[k:, k], beta, r, y, rr, f.  rec[0..3] = the step's record.
+ * One host synchronisation. */
+int kh_idrs_orth(kh_ctx ctx, kh_vec P, int64_t pcol, kh_vec G, int64_t gcol, kh_vec U, int64_t ucol, kh_vec R, int64_t rcol,
+                 kh_vec YK, int64_t ycol, kh_vec T, int64_t tcol, kh_vec SC, int s, int k, double bnorm, double tol,
+                 double* rec);
+/* position s from t = A^ r on (the caller's product).  Clears the stop word and the counter first.  rec[0..3] = the record.
+ * One host synchronisation. */
+int kh_idrs_omega(kh_ctx ctx, kh_vec P, int64_t pcol, kh_vec G, int64_t gcol, kh_vec U, int64_t ucol, kh_vec R, int64_t rcol,
+                  kh_vec YK, int64_t ycol, kh_vec T, int64_t tcol, kh_vec SC, int s, double bnorm, double tol, double* rec);
+/* nsteps <= KH_IDRS_RUN_MAX consecutive positions from `pos` on (0 <= pos <= s, wrapping from s to 0) for a real kh_mat
+ * (CSR, dense, diagonal), the operator applied in between, and ONE copy to the host at the end: out[0] = the number of steps
+ * done (fewer than nsteps after a stop), out[1 + 4 i ..] = the record of step i.  out holds 1 + 4 * nsteps doubles.  The
+ * stop word is cleared on entry: a caller who does not accept a stop calls again from the position after the last step
+ * done.  The same bits as the pieces above with kh_apply in between. */
+int kh_idrs_run(kh_ctx ctx, kh_mat A, kh_vec P, int64_t pcol, kh_vec G, int64_t gcol, kh_vec U, int64_t ucol, kh_vec R,
+                int64_t rcol, kh_vec YK, int64_t ycol, kh_vec T, int64_t tcol, kh_vec SC, int s, int pos, int nsteps,
+                double bnorm, double tol, double* out);
+
 /* ---- complex (c128) twin of the hot path ------------------------------------------------- */
 /* KryPy's kernels are dtype-generic NumPy (H/V are allocated with the common dtype of A, v, M:
  * utils.py:893-905, complex inner products are X^H Y: utils.py:183).  A complex N-vector block is

@@ -11,6 +11,6 @@ There is no CPU fallback: without ``libkrylov_hip.so`` and an MI355X every solve
 """
 from . import deflation, linsys, recycling, utils
 from .__about__ import __version__
-from ._convenience import bicgstab, cg, gmres, minres
+from ._convenience import bicgstab, cg, gmres, idrs, minres
 
-__all__ = ["linsys", "deflation", "recycling", "utils", "cg", "minres", "gmres", "bicgstab", "__version__"]
+__all__ = ["linsys", "deflation", "recycling", "utils", "cg", "minres", "gmres", "bicgstab", "idrs", "__version__"]

@@ -3,13 +3,13 @@
 Same signatures, defaults and return convention: ``(x or None, solver)`` where ``x`` has the
 shape of ``b`` and is ``None`` when ``solver.resnorms[-1] >= tol``; a ``ConvergenceError``
 raised by the solver is *not* caught (as in the reference).  ``Mr`` is accepted and dropped,
-like in the reference (``_convenience.py:48-56,112-120,177-185``).  ``bicgstab`` has no counterpart there: it passes
-``Mr`` through.
+like in the reference (``_convenience.py:48-56,112-120,177-185``).  ``bicgstab`` and ``idrs`` have no counterpart there: they
+pass ``Mr`` through.
 """
 import numpy
 
 from .deflation import DeflatedCg, DeflatedGmres, DeflatedMinres
-from .linsys import Bicgstab, Cg, Gmres, LinearSystem, Minres
+from .linsys import Bicgstab, Cg, Gmres, Idrs, LinearSystem, Minres
 
 
 def wrap_inner_product(inner):
@@ -83,4 +83,13 @@ def bicgstab(A, b, Ml=None, Mr=None, exact_solution=None, x0=None, tol=1e-5, max
     _, _, x0 = _prepare(A, b, None, None, x0)
     linear_system = LinearSystem(A=A, b=b, Ml=Ml, Mr=Mr, exact_solution=exact_solution)
     out = Bicgstab(linear_system, x0=x0, tol=tol, maxiter=maxiter, explicit_residual=use_explicit_residual)
+    return _result(out, b)
+
+
+def idrs(A, b, s=4, shadow=None, seed=0, steps_per_call=None, Ml=None, Mr=None, exact_solution=None, x0=None, tol=1e-5,
+         maxiter=None, use_explicit_residual=False):
+    _, _, x0 = _prepare(A, b, None, None, x0)
+    linear_system = LinearSystem(A=A, b=b, Ml=Ml, Mr=Mr, exact_solution=exact_solution)
+    out = Idrs(linear_system, s=s, shadow=shadow, seed=seed, steps_per_call=steps_per_call, x0=x0, tol=tol, maxiter=maxiter,
+               explicit_residual=use_explicit_residual)
     return _result(out, b)

@@ -34,6 +34,11 @@ CG_NONFINITE_PAP, CG_NONPOSITIVE_PAP, CG_NONFINITE_RHO, CG_NEGATIVE_RHO = 1, 2, 
 CG_STEP_CLAMPED = 16
 # sanity word of the BiCGStab entries (KH_BICG_* of the header)
 BICG_NONFINITE_SIGMA, BICG_ALPHA_CLAMPED, BICG_OMEGA_CLAMPED, BICG_RHO_ZERO = 1, 2, 4, 8
+# IDR(s): flags of a step's record, sizes, and the layout of the scalar block (KH_IDRS_* of the header, csrc/idrs.h)
+IDRS_PIVOT_ZERO, IDRS_OMEGA_CLAMPED, IDRS_OMEGA_ZERO, IDRS_NONFINITE = 1, 2, 4, 8
+IDRS_SMAX, IDRS_RUN_MAX, IDRS_NSCAL = 8, 64, 361
+IDRS_LAYOUT = dict(M=0, F=64, C=72, H=80, A=88, OM=96, RR=97, THETA=98, PHI=99, BETA=100, FLAGS=101, TMP=102, STOP=103,
+                   COUNT=104, REC=105)
 # stop reasons of kh_gmres_cycle (KH_CYCLE_* of the header)
 CYCLE_LIMIT, CYCLE_TOL, CYCLE_CHECK = 0, 1, 2
 
@@ -157,6 +162,11 @@ _SIGNATURES = {
     "kh_bicgstab_full": [_H, _H, _I64, _H, _I64, _H, _I64, _H, _I64, _H, _I64, _H, _I64, _INT, _c_double_p],
     "kh_bicgstab_step": [_H, _H, _H, _I64, _H, _I64, _H, _I64, _H, _I64, _H, _I64, _H, _I64, _H, _I64, _INT, _D, _D, _D,
                          _c_double_p],
+    "kh_idrs_init": [_H] + [_H, _I64] * 6 + [_H, _INT, _c_double_p],
+    "kh_idrs_dir": [_H] + [_H, _I64] * 6 + [_H, _INT, _INT],
+    "kh_idrs_orth": [_H] + [_H, _I64] * 6 + [_H, _INT, _INT, _D, _D, _c_double_p],
+    "kh_idrs_omega": [_H] + [_H, _I64] * 6 + [_H, _INT, _D, _D, _c_double_p],
+    "kh_idrs_run": [_H, _H] + [_H, _I64] * 6 + [_H, _INT, _INT, _INT, _D, _D, _c_double_p],
     "kh_bench_kernel": [_H, _INT, _H, _H, _INT, _c_double_p],
     "kh_bench_arnoldi": [_H, _H, _H, _H, _I64, _INT, _INT, _c_double_p],
     # complex (c128) side: vectors are real blocks of length 2N (interleaved re, im)
@@ -1328,6 +1338,54 @@ class Context(object):
             tcol, YK.handle, ycol, 1 if first else 0, float(beta), float(omega_prev), float(rho), _dptr(out)),
             "kh_bicgstab_step")
         return tuple(float(x) for x in out[:6]) + (int(out[6]),)
+
+    # ---- IDR(s) (real fp64; the header has the iteration).  ``state`` = (P, pcol, G, gcol, U, ucol, R, rcol, YK, ycol, T,
+    # tcol, SC, s): the shadow space, G and U with s columns each from their column on, r, y, the scratch column that takes
+    # the operator products, and the scalar block (one zero-initialised column of IDRS_NSCAL doubles).
+    def _idrs_state(self, what, state):
+        P, pcol, G, gcol, U, ucol, R, rcol, YK, ycol, T, tcol, SC, s = state
+        if _same_dtype(what, P, G, U, R, YK, T, SC):
+            raise BackendError("%s: real blocks expected" % what)
+        return (P.handle, pcol, G.handle, gcol, U.handle, ucol, R.handle, rcol, YK.handle, ycol, T.handle, tcol, SC.handle,
+                int(s))
+
+    @staticmethod
+    def _idrs_record(rec):
+        return float(rec[0]), float(rec[1]), float(rec[2]), int(rec[3])
+
+    def idrs_init(self, state):
+        """``M = I``, ``om = 1``, ``f = P^T r``, stop word and counter cleared (``kh_idrs_init``).  Returns ``<r, r>``."""
+        out = numpy.empty(1, dtype=numpy.float64)
+        _check(self._lib, self._lib.kh_idrs_init(self._h, *self._idrs_state("idrs_init", state), _dptr(out)), "kh_idrs_init")
+        return float(out[0])
+
+    def idrs_dir(self, state, k):
+        """Position ``k < s`` up to the operator: ``c`` and ``u_k`` (``kh_idrs_dir``); the caller then forms
+        ``t = A^ u_k``."""
+        _check(self._lib, self._lib.kh_idrs_dir(self._h, *self._idrs_state("idrs_dir", state), int(k)), "kh_idrs_dir")
+
+    def idrs_orth(self, state, k, bnorm, tol):
+        """Position ``k < s`` from the product ``t`` on (``kh_idrs_orth``).  Returns the step's record
+        ``(rr, M_kk, f_k, flags)`` (``flags``: ``IDRS_*``)."""
+        out = numpy.empty(4, dtype=numpy.float64)
+        _check(self._lib, self._lib.kh_idrs_orth(self._h, *self._idrs_state("idrs_orth", state), int(k), float(bnorm),
+                                                 float(tol), _dptr(out)), "kh_idrs_orth")
+        return self._idrs_record(out)
+
+    def idrs_omega(self, state, bnorm, tol):
+        """Position ``s`` from ``t = A^ r`` on (``kh_idrs_omega``).  Returns the record ``(rr, theta, phi, flags)``."""
+        out = numpy.empty(4, dtype=numpy.float64)
+        _check(self._lib, self._lib.kh_idrs_omega(self._h, *self._idrs_state("idrs_omega", state), float(bnorm), float(tol),
+                                                  _dptr(out)), "kh_idrs_omega")
+        return self._idrs_record(out)
+
+    def idrs_run(self, A, state, pos, nsteps, bnorm, tol):
+        """``nsteps`` consecutive positions from ``pos`` on for a real device matrix, one copy to the host at the end
+        (``kh_idrs_run``).  Returns the records of the steps done: fewer than ``nsteps`` after a stop."""
+        out = numpy.zeros(1 + 4 * max(int(nsteps), 1), dtype=numpy.float64)
+        _check(self._lib, self._lib.kh_idrs_run(self._h, A.handle, *self._idrs_state("idrs_run", state), int(pos), int(nsteps),
+                                                float(bnorm), float(tol), _dptr(out)), "kh_idrs_run")
+        return [self._idrs_record(out[1 + 4 * i:5 + 4 * i]) for i in range(int(out[0]))]
 
     def bench_kernel(self, which, V, W, reps):
         ms = _D(0.0)

@@ -1,7 +1,9 @@
-// BiCGStab (bicgstab.hip): where the iteration's scalars live on the device, and the sanity word the host forms beside them.
+// BiCGStab (bicgstab.hip): where the iteration's scalars live on the device, the sanity word the host forms beside them, and the
+// two-sum kernel that idrs.hip launches as well.
 #pragma once
 #include <cmath>
 
+#include "kernels.h"
 #include "krylov_hip.h"
 
 namespace kh {
@@ -23,6 +25,26 @@ static inline int bicg_sanity_full(double theta, double phi, double rho_new) {
     if (!std::isfinite(theta / phi)) f |= KH_BICG_OMEGA_CLAMPED;
     if (!std::isfinite(rho_new) || rho_new == 0.0) f |= KH_BICG_RHO_ZERO;
     return f;
+}
+
+// two partials per workgroup, <t, s> in part0 and <t, t> in part1.  2 vector passes: s, t read.  (Here because idrs.hip takes
+// the theta and phi of its dimension-reduction step from the same kernel.)
+static __global__ __launch_bounds__(BS) void k_bicg_dots(int64_t n, const double* __restrict__ s, const double* __restrict__ t,
+                                                         double* __restrict__ part0, double* __restrict__ part1) {
+    __shared__ double sm0[4], sm1[4];         // one LDS row per sum: block_sum ends with thread 0 still reading its row
+    const int64_t stride = (int64_t)gridDim.x * BS;
+    double a0 = 0.0, a1 = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x; i < n; i += stride) {
+        const double tv = t[i];
+        a0 = fma(tv, s[i], a0);
+        a1 = fma(tv, tv, a1);
+    }
+    const double r0 = block_sum(a0, sm0);
+    const double r1 = block_sum(a1, sm1);
+    if (threadIdx.x == 0) {
+        part0[blockIdx.x] = r0;
+        part1[blockIdx.x] = r1;
+    }
 }
 
 }  // namespace kh

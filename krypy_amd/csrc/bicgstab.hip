@@ -22,7 +22,6 @@
 #include <algorithm>
 #include <cmath>
 
-#include "kernels.h"
 #include "krylov_steps.h"
 #include "bicgstab.h"
 
@@ -61,25 +60,6 @@ __global__ __launch_bounds__(BS) void k_bicg_half(int64_t n, double rho, double*
     }
     const double sum = block_sum(acc, sm);
     if (threadIdx.x == 0) part_out[blockIdx.x] = sum;
-}
-
-// two partials per workgroup, <t, s> in part0 and <t, t> in part1.  2 vector passes: s, t read.
-__global__ __launch_bounds__(BS) void k_bicg_dots(int64_t n, const double* __restrict__ s, const double* __restrict__ t,
-                                                  double* __restrict__ part0, double* __restrict__ part1) {
-    __shared__ double sm0[4], sm1[4];         // one LDS row per sum: block_sum ends with thread 0 still reading its row
-    const int64_t stride = (int64_t)gridDim.x * BS;
-    double a0 = 0.0, a1 = 0.0;
-    for (int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x; i < n; i += stride) {
-        const double tv = t[i];
-        a0 = fma(tv, s[i], a0);
-        a1 = fma(tv, tv, a1);
-    }
-    const double r0 = block_sum(a0, sm0);
-    const double r1 = block_sum(a1, sm1);
-    if (threadIdx.x == 0) {
-        part0[blockIdx.x] = r0;
-        part1[blockIdx.x] = r1;
-    }
 }
 
 // omega = theta / phi (from device memory, clamped as alpha); y = (y + alpha * p) + omega * s; r = s - omega * t; two partials

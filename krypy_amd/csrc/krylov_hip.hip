@@ -1059,6 +1059,7 @@ int kh_ctx_get(kh_ctx ctx, const char* key, int64_t* value) {
     else if (!strcmp(key, "n_minres_cycle_steps")) *value = ctx->n_minres_cycle_steps;
     else if (!strcmp(key, "n_cg_cycle_steps")) *value = ctx->n_cg_cycle_steps;
     else if (!strcmp(key, "n_bicgstab_steps")) *value = ctx->n_bicgstab_steps;
+    else if (!strcmp(key, "n_idrs_steps")) *value = ctx->n_idrs_steps;
     else if (!strcmp(key, "mgs_lowsync")) *value = ctx->mgs_lowsync;
     else if (!strcmp(key, "proj_reg")) *value = ctx->proj_reg;
     else if (!strcmp(key, "xr")) *value = ctx->xr_on;

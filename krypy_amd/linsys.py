@@ -6,7 +6,7 @@ solver object *is* the result.  All N-vectors stay in HBM between iterations; at
 that the reference exposes as ndarrays (``xk``, ``x0``, ``MMlr0``, ``Mlr0``, ``V``, ``P``,
 ``LinearSystem.Mlb`` ...) are downloaded lazily on first access.  The Hessenberg matrix,
 Givens rotations and the small triangular solves stay on the host like in the reference.
-``Bicgstab`` has no counterpart in the reference (same skeleton, same attributes).
+``Bicgstab`` and ``Idrs`` have no counterpart in the reference (same skeleton, same attributes).
 
 Reference lines are cited as ``linsys.py:<line>`` (= ``/root/reference/krypy/linsys.py``).
 """
@@ -21,7 +21,7 @@ from . import _hip, utils
 from .utils import DVec
 
 __all__ = ["LinearSystem", "TimedLinearSystem", "ConvertedTimedLinearSystem", "Cg", "Minres", "Gmres",
-           "RestartedGmres", "Bicgstab"]
+           "RestartedGmres", "Bicgstab", "Idrs"]
 
 
 class _LazyHost(object):
@@ -737,6 +737,148 @@ class Bicgstab(_KrylovSolver):
         """Number of operations needed for nsteps of BiCGStab."""
         return {"A": 1 + 2 * nsteps, "M": 2, "Ml": 2 + 2 * nsteps, "Mr": 1 + 2 * nsteps,
                 "ip_B": 2 + 5 * nsteps, "axpy": 1 + 6 * nsteps}
+
+
+class Idrs(_KrylovSolver):
+    r"""IDR(s) with bi-orthogonalisation (van Gijzen & Sonneveld 2011) for non-symmetric systems; the reference has no
+    counterpart.
+
+    A short recurrence on :math:`\hat A = M_l A M_r` with ``3 s + 3`` vectors at any iteration count; one ITERATION is one
+    operator application and a cycle has ``s + 1`` of them (``include/krylov_hip.h`` has the iteration; the order of its
+    operations is fixed).  Every scalar of the recurrence is formed on the device.  With a plain device matrix as
+    :math:`\hat A` (and no ``explicit_residual``, no ``exact_solution``) ``steps_per_call`` iterations (default ``s + 1``, at
+    most 64) are ONE device call and one host synchronisation (``idrs_run``); the device stops by itself after the iteration
+    that reaches ``tol`` or raises a breakdown flag.  Any other operator is applied through its own ``_apply_dev`` with the
+    fused kernels around it (one synchronisation per iteration).  Both paths compute the same bits.  Real data, Euclidean
+    inner product.
+
+    :param s: dimension of the shadow space, 1 ... 8 (``s = 1`` is mathematically BiCGStab).
+    :param shadow: the shadow space as a real ``N x s`` array, or as a device block of that shape (used as it is: solves
+      that share a shadow space upload it once); default ``utils.idrs_shadow(N, s, seed)``.
+
+    ``idrs_trace`` holds the last 16 iterations' ``(iteration, position, rr, M_kk or theta, f_k or phi, flags)``; a
+    breakdown flag (``_hip.IDRS_*``) with a residual above ``tol`` raises :class:`~utils.ConvergenceError` with them.
+    """
+
+    def __init__(self, linear_system, s=4, shadow=None, seed=0, steps_per_call=None, x0=None, tol=1e-5, maxiter=None,
+                 explicit_residual=False, store_arnoldi=False):
+        if not isinstance(linear_system, LinearSystem):
+            raise utils.ArgumentError("linear_system is not an instance of LinearSystem")
+        ls = linear_system
+        if not (isinstance(ls.M, utils.IdentityLinearOperator) and isinstance(ls.Minv, utils.IdentityLinearOperator)):
+            raise utils.ArgumentError("Idrs: M / Minv change the inner product, which IDR(s) does not use; pass the "
+                                      "preconditioner as Ml (left) or Mr (right) instead")
+        if not (ls.ip_B is None or isinstance(ls.ip_B, utils.IdentityLinearOperator)):
+            raise utils.ArgumentError("Idrs: only the Euclidean inner product (ip_B=None) is implemented; use Gmres for "
+                                      "another inner product")
+        if store_arnoldi:
+            raise utils.ArgumentError("Idrs: store_arnoldi=True is not available, IDR(s) builds no Arnoldi relation; "
+                                      "use Gmres for V and H")
+        utils._require_real(ls.dtype, "Idrs: the linear system (A, b, Ml or Mr)")
+        utils._require_real(getattr(x0, "dtype", numpy.float64), "Idrs: x0")
+        if isinstance(s, bool) or not isinstance(s, (int, numpy.integer)) or not 1 <= s <= _hip.IDRS_SMAX:
+            raise utils.ArgumentError("Idrs: s = %r is outside 1 ... %d" % (s, _hip.IDRS_SMAX))
+        self.s = s = int(s)
+        if shadow is None:
+            shadow = utils.idrs_shadow(ls.N, s, seed)
+        device = hasattr(shadow, "handle") and hasattr(shadow, "ncols")      # a device block: used as it is, never written
+        if not device:
+            shadow = numpy.asarray(shadow)
+        if numpy.dtype(shadow.dtype).kind not in "fiu":
+            raise utils.ArgumentError("Idrs: shadow has dtype %s, a real array is expected" % shadow.dtype)
+        shape = (shadow.n, shadow.ncols) if device else shadow.shape
+        if shape != (ls.N, s):
+            raise utils.ArgumentError("Idrs: shadow has shape %r, (N, s) = %r is expected" % (shape, (ls.N, s)))
+        self.shadow = shadow if device else numpy.asfortranarray(shadow, dtype=numpy.float64)
+        if steps_per_call is None:
+            steps_per_call = s + 1
+        if (isinstance(steps_per_call, bool) or not isinstance(steps_per_call, (int, numpy.integer))
+                or not 1 <= steps_per_call <= _hip.IDRS_RUN_MAX):
+            raise utils.ArgumentError("Idrs: steps_per_call = %r is outside 1 ... %d" % (steps_per_call, _hip.IDRS_RUN_MAX))
+        self.steps_per_call = int(steps_per_call)
+        super(Idrs, self).__init__(ls, x0=x0, tol=tol, maxiter=maxiter, explicit_residual=explicit_residual)
+
+    def __repr__(self):
+        return self._repr("krypy IDR(s) object", extra=["    s: {}".format(self.s)])
+
+    _FLAG_NAMES = ((_hip.IDRS_PIVOT_ZERO, "M_kk is zero or not finite"), (_hip.IDRS_OMEGA_CLAMPED, "<t, t> = 0: omega clamped"),
+                   (_hip.IDRS_OMEGA_ZERO, "omega = 0"), (_hip.IDRS_NONFINITE, "a sum is not finite"))
+
+    def _solve(self):
+        ls = self.linear_system
+        ctx = self._ctx
+        N, s = ls.N, self.s
+        bdt = self._bdt
+        bnorm = float(ls.MMlb_norm)
+        self.idrs_trace = trace = collections.deque(maxlen=16)
+
+        yk = DVec(ctx.alloc(N, 1, dtype=bdt))
+        self.iter = 0
+        if not (self.resnorms[-1] > self.tol and self.iter < self.maxiter):
+            if not _is_set(self, "xk"):
+                self.xk = self._get_xk(yk)
+            return
+        r = _dev_of(self, "Mlr0", ctx).astype(bdt).copy()
+        P = self.shadow if hasattr(self.shadow, "handle") else ctx.upload(self.shadow)
+        G, U = ctx.alloc(N, s, dtype=bdt), ctx.alloc(N, s, dtype=bdt)
+        t = DVec(ctx.alloc(N, 1, dtype=bdt, zero=False))
+        SC = ctx.alloc(_hip.IDRS_NSCAL, 1, dtype=bdt)
+        state = (P, 0, G, 0, U, 0, r.block, r.col, yk.block, yk.col, t.block, t.col, SC, s)
+        ctx.idrs_init(state)
+
+        # runs of iterations in one device call when the operator is a plain device matrix and nothing but the recurrence's
+        # residual norm is wanted of an iteration
+        Amat = self.MlAMr._device_matrix(ctx, bdt)
+        runs = (Amat is not None and hasattr(ctx, "idrs_run") and not self.explicit_residual
+                and ls.exact_solution is None)
+        tol = float(self.tol)
+        pos = 0
+        while self.resnorms[-1] > self.tol and self.iter < self.maxiter:
+            # (the iteration with iter + 1 == maxiter ends with the explicit residual of ITS iterate: never inside a run)
+            nrun = min(self.steps_per_call, self.maxiter - 1 - self.iter) if runs else 0
+            if nrun > 0:
+                records = ctx.idrs_run(Amat, state, pos, nrun, bnorm, tol)
+            elif pos < s:
+                ctx.idrs_dir(state, pos)
+                self.MlAMr._apply_dev(U, pos, t.block, t.col, 1)
+                records = [ctx.idrs_orth(state, pos, bnorm, tol)]
+            else:
+                self.MlAMr._apply_dev(r.block, r.col, t.block, t.col, 1)
+                records = [ctx.idrs_omega(state, bnorm, tol)]
+            if not records:
+                raise utils.RuntimeError("Idrs: the device recorded no step")
+            for rr, x1, x2, flags in records:
+                k = self.iter
+                trace.append((k, pos, rr, x1, x2, flags))
+                resnorm = numpy.sqrt(numpy.float64(abs(rr)))
+                if flags and not resnorm / bnorm <= self.tol:
+                    self.xk = self._get_xk(yk)
+                    raise utils.ConvergenceError(
+                        "IDR(s) breakdown in iteration %d (%s; flags %d); last steps (iteration, position, rr, M_kk or theta, "
+                        "f_k or phi, flags): %s" % (k, "; ".join(text for bit, text in self._FLAG_NAMES if flags & bit), flags,
+                                                    list(trace)), self)
+                try:
+                    self._finalize_iteration(yk, resnorm)
+                except utils.ConvergenceError:
+                    self.iter += 1                       # the solver an error carries counts the iterations it has done
+                    raise
+                self.iter += 1
+                pos = (pos + 1) % (s + 1)
+
+        if not _is_set(self, "xk"):      # (reading self.xk would download it)
+            self.xk = self._get_xk(yk)
+
+    @staticmethod
+    def operations(nsteps, s=4):
+        """Number of operations needed for ``nsteps`` iterations (operator applications) of IDR(s).  A cycle of ``s + 1``
+        iterations takes ``s (s + 1) + s + 3`` inner products (the block inner products ``P^T t`` and ``P^T r`` counted
+        column by column, ``<r, r>`` after every iteration, ``<t, r>`` and ``<t, t>``) and ``2 s^2 + 3 s + 2`` vector
+        updates; ``nsteps`` iterations are charged their share of a cycle, rounded up.  The setup takes ``s + 3`` inner
+        products."""
+        cyc = s + 1
+        return {"A": 1 + nsteps, "M": 2, "Ml": 2 + nsteps, "Mr": 1 + nsteps,
+                "ip_B": 3 + s + -(-nsteps * (s * (s + 1) + s + 3) // cyc),
+                "axpy": 1 + -(-nsteps * (2 * s * s + 3 * s + 2) // cyc)}
 
 
 class _ArnoldiBasisMixin(object):

@@ -31,7 +31,7 @@ __all__ = [
     "ZeroLinearOperator", "Projection", "arnoldi", "arnoldi_res", "find_common_dtype",
     "get_linearoperator", "inner", "ip_euclid", "norm", "norm_squared", "orthonormality", "qr",
     "shape_vec", "shape_vecs", "DVec", "Timer", "Timings", "TimedLinearOperator", "ritz",
-    "hegedus", "angles", "TriangularSolveOperator", "ilu_operator", "ilu0", "ilu0_operator", "Ilu0Preconditioner", "ilu0_preconditioner", "spai", "spai_operator", "fsai", "fsai_operator", "ChebyshevOperator", "chebyshev_operator",
+    "hegedus", "angles", "TriangularSolveOperator", "ilu_operator", "ilu0", "ilu0_operator", "Ilu0Preconditioner", "ilu0_preconditioner", "spai", "spai_operator", "fsai", "fsai_operator", "ChebyshevOperator", "chebyshev_operator", "idrs_shadow",
 ]
 
 
@@ -115,6 +115,16 @@ def _require_real(dtype, what):
         raise NotImplementedError(
             "%s is complex: this part of the MI355X path is real fp64 only; there is no CPU "
             "fallback." % what)
+
+
+def idrs_shadow(N, s, seed=0):
+    """The default shadow space of :class:`~linsys.Idrs`: an ``N x s`` matrix of ``numpy.random.RandomState(seed)`` normal
+    entries, orthonormalised by ``numpy.linalg.qr``."""
+    N, s = int(N), int(s)
+    if not 1 <= s <= N:
+        raise ArgumentError("idrs_shadow: s = %d columns of length N = %d (1 <= s <= N expected)" % (s, N))
+    Q, _ = numpy.linalg.qr(numpy.random.RandomState(seed).randn(N, s))
+    return numpy.asfortranarray(Q)
 
 
 def _bdt(*dtypes):
