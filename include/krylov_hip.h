@@ -40,6 +40,7 @@ typedef struct kh_vec_s* kh_vec;
 typedef struct kh_proj_s* kh_proj;
 typedef struct kh_tri_s* kh_tri;
 typedef struct kh_ilu0_s* kh_ilu0;
+typedef struct kh_bjac_s* kh_bjac;
 
 typedef enum {
     KH_OK = 0,
@@ -709,6 +710,50 @@ int kh_fsai_build(kh_ctx ctx, int64_t n, int64_t nnz, const int32_t* indptr, con
  * substitution takes L unconjugated. */
 int kh_zfsai_build(kh_ctx ctx, int64_t n, int64_t nnz, const int32_t* indptr, const int32_t* indices, const double* data_re_im,
                    int64_t pnnz, const int32_t* pindptr, const int32_t* pindices, double* u_out_re_im, double* d_out, int64_t info[8]);
+
+/* ---- Block-Jacobi preconditioner: blocks inverted and applied on the device ------------------------------------------------- */
+/* All entry points serve the M, Ml, Mr hooks of krypy/linsys.py; no reference counterpart (the reference calls the user's
+ * function on host arrays).  For a partition of 0 .. n into nblk consecutive ranges blkptr[0 .. nblk] (blkptr[0] = 0,
+ * blkptr[nblk] = n, strictly increasing, every block of 1 .. 32 rows) the handle holds the inverses of the diagonal blocks
+ * A[blkptr[g] : blkptr[g+1], blkptr[g] : blkptr[g+1]] on the device, in the layout its apply kernel reads.  A handle type of its
+ * own: a kh_bjac is not a kh_mat and kh_apply never sees one.  Contract (the order of every operation), layout and kernels:
+ * krypy_amd/csrc/bjac.h, bjac.hip. */
+/* M / Ml / Mr hooks, no reference counterpart.  A (n, nnz, indptr, indices, data) as CSR with SORTED, duplicate-free int32
+ * indices; stored zeros are kept, entries a block's rows do not store are 0.  Validates, uploads, and inverts ALL blocks in ONE
+ * launch: one block per group of W lanes (W the smallest of 1, 2, 4, 8, 16, 32 that holds the largest block), Gauss-Jordan
+ * elimination with row pivoting (pivot: the largest |re| + |im| of the column at or below the diagonal, the smallest row among
+ * equals, a NaN counting as the largest), every multiply, add and divide rounded on its own, complex products as
+ * (ac - bd, ad + bc), 1 / pivot by Smith's formula.  info = n, nnz, nblk, rows of the largest block, W, workgroups of the build
+ * launch, device bytes held, smallest block that is BROKEN or -1.  A block is broken when a pivot is 0 or not finite; that is
+ * NOT an error of the call: it returns 0 and the inverse holds what IEEE arithmetic makes of it.  KH_ERR_ARG (the row or the
+ * block named): n, nnz or nblk out of int32 range, unsorted or duplicate indices, a column out of range, a blkptr that does not
+ * start at 0, does not end at n, is not strictly increasing or has a block above 32 rows; KH_ERR_NOMEM: an allocation failed
+ * (nothing stays allocated on any way out); KH_ERR_UNSUPPORTED: the context has a communicator.  Counters (kh_ctx_get):
+ * "n_bjac_build" build launches, "bjac_device_us" the device time of the last one (HIP events around it). */
+int kh_bjac_create(kh_ctx ctx, int64_t n, int64_t nnz, const int32_t* indptr, const int32_t* indices, const double* data, int64_t nblk,
+                   const int32_t* blkptr, kh_bjac* out, int64_t info[8]);
+/* M / Ml / Mr hooks with complex data, no reference counterpart: the same with (re, im) pairs; the handle is then complex. */
+int kh_zbjac_create(kh_ctx ctx, int64_t n, int64_t nnz, const int32_t* indptr, const int32_t* indices, const double* data_re_im,
+                    int64_t nblk, const int32_t* blkptr, kh_bjac* out, int64_t info[8]);
+/* M / Ml / Mr hooks, no reference counterpart.  New values at the SAME CSR positions ((re, im) pairs for a complex handle): one
+ * upload, the build launch again, nothing re-analysed or allocated; kh_bjac_info then gives the refreshed info. */
+int kh_bjac_update(kh_bjac h, const double* data);
+/* M / Ml / Mr hooks, no reference counterpart: the info block of kh_bjac_create as of the last build. */
+int kh_bjac_info(kh_bjac h, int64_t info[8]);
+/* M / Ml / Mr hooks, no reference counterpart.  Y[:, ycol + c] = D^-1 X[:, xcol + c], c < ncols, one launch per column:
+ * y_i = ((0 + b[i][0] x_0) + b[i][1] x_1) + ... over the columns of row i's block in rising order, separate multiply and add -
+ * the bits of kh_apply with the block-diagonal CSR matrix that stores every entry of every inverse.  Complex handles take the
+ * (re, im) views of length 2 n.  Rows [n, ld) of Y are not written.  KH_ERR_ARG: another context's handle; the length of the
+ * blocks does not match (also: a real handle on complex blocks or the reverse); X and Y the same block with overlapping column
+ * ranges (the kernel does not work in place).  A handle with a broken block is applied as it is.  Counter: "n_bjac_apply"
+ * columns. */
+int kh_bjac_apply(kh_ctx ctx, kh_bjac h, kh_vec X, int64_t xcol, kh_vec Y, int64_t ycol, int64_t ncols);
+/* M / Ml / Mr hooks, no reference counterpart (diagnostics, tests, the matrix form): downloads the inverses as dense row-major
+ * m_g x m_g arrays, one after another in block order (sum of m_g^2 values, (re, im) pairs for a complex handle), whatever the
+ * device layout is. */
+int kh_bjac_values(kh_bjac h, double* out);
+/* M / Ml / Mr hooks, no reference counterpart: releases everything the handle holds on the device (waits for the stream first). */
+int kh_bjac_free(kh_bjac h);
 
 /* ---- Chebyshev polynomial preconditioner -------------------------------------------------------------------------------- */
 /* Both entry points serve the M, Ml, Mr hooks of krypy/linsys.py: z = p(A) r as m steps of the Chebyshev iteration for A z = r

@@ -132,6 +132,14 @@ _SIGNATURES = {
     "kh_ilu0_values": [_H, _c_double_p],
     "kh_ilu0_info": [_H, _c_int64_p],
     "kh_ilu0_free": [_H],
+    # block-Jacobi preconditioner: blocks inverted and applied on the device (csrc/bjac.hip)
+    "kh_bjac_create": [_H, _I64, _I64, _c_int32_p, _c_int32_p, _c_double_p, _I64, _c_int32_p, ctypes.POINTER(_H), _c_int64_p],
+    "kh_zbjac_create": [_H, _I64, _I64, _c_int32_p, _c_int32_p, _c_double_p, _I64, _c_int32_p, ctypes.POINTER(_H), _c_int64_p],
+    "kh_bjac_update": [_H, _c_double_p],
+    "kh_bjac_info": [_H, _c_int64_p],
+    "kh_bjac_apply": [_H, _H, _H, _I64, _H, _I64, _I64],
+    "kh_bjac_values": [_H, _c_double_p],
+    "kh_bjac_free": [_H],
     # sparse approximate inverse on a fixed pattern (csrc/spai.hip)
     "kh_spai_build": [_H, _I64, _I64, _c_int32_p, _c_int32_p, _c_double_p, _I64, _c_int32_p, _c_int32_p, _c_double_p, _c_int64_p],
     "kh_zspai_build": [_H, _I64, _I64, _c_int32_p, _c_int32_p, _c_double_p, _I64, _c_int32_p, _c_int32_p, _c_double_p, _c_int64_p],
@@ -376,6 +384,35 @@ class DeviceIlu0(object):
         try:
             if self.handle is not None and self.ctx._alive:
                 self.ctx._lib.kh_ilu0_free(self.handle)
+        except Exception:
+            pass
+        self.handle = None
+
+
+def _bjac_info(buf):
+    return dict(n=buf[0], nnz=buf[1], nblk=buf[2], max_block=buf[3], group_width=buf[4], workgroups=buf[5],
+                device_bytes=buf[6], first_broken_block=buf[7])
+
+
+class DeviceBjac(object):
+    """A block-Jacobi preconditioner on the device (``kh_bjac``): the inverses of the diagonal blocks of a matrix, built by
+    ``Context.bjac_create``, rebuilt for new values by ``Context.bjac_update``, applied by ``Context.bjac_apply``."""
+
+    def __init__(self, ctx, handle, shape, nnz, dtype, blkptr):
+        self.ctx, self.handle, self.shape, self.nnz = ctx, handle, shape, nnz
+        self.dtype = numpy.dtype(dtype)
+        self.blkptr = blkptr
+
+    def info(self):
+        """The figures of the last build (``kh_bjac_info``)."""
+        buf = (ctypes.c_int64 * 8)()
+        _check(self.ctx._lib, self.ctx._lib.kh_bjac_info(self.handle, buf), "kh_bjac_info")
+        return _bjac_info(buf)
+
+    def __del__(self):
+        try:
+            if self.handle is not None and self.ctx._alive:
+                self.ctx._lib.kh_bjac_free(self.handle)
         except Exception:
             pass
         self.handle = None
@@ -869,6 +906,58 @@ class Context(object):
             raise BackendError("ilu0_solve: %s preconditioner on %s blocks" % (h.dtype, X.dtype))
         _check(self._lib, self._lib.kh_ilu0_solve(self._h, h.handle, X.handle, xcol, Y.handle, ycol, ncols),
                "kh_ilu0_solve")
+
+    def bjac_create(self, A, blkptr):
+        """The block-Jacobi preconditioner of the square SciPy CSR matrix ``A`` (sorted, duplicate-free indices) for the
+        partition ``blkptr`` (``blkptr[0] = 0 < ... < blkptr[-1] = n``, blocks of at most 32 rows): the diagonal blocks are
+        inverted on the device in one launch and stay there (``kh_bjac_create`` / ``kh_zbjac_create``).  Returns
+        ``(handle, info)``.  A broken block (a pivot that is zero or not finite) is not an error here:
+        ``info["first_broken_block"]`` names the smallest one (-1: none)."""
+        if A.shape[0] != A.shape[1]:
+            raise BackendError("bjac_create: a square matrix expected, got %s" % (A.shape,))
+        indptr = numpy.ascontiguousarray(A.indptr, dtype=numpy.int32)
+        indices = numpy.ascontiguousarray(A.indices, dtype=numpy.int32)
+        blk = numpy.asarray(blkptr)
+        if blk.ndim != 1 or blk.size < 2 or blk.dtype.kind not in "iu":
+            raise BackendError("bjac_create: blkptr must be an integer array of at least two entries")
+        if blk.min() < 0 or blk.max() > 0x7fffffff:
+            raise BackendError("bjac_create: blkptr leaves the int32 range")
+        blk = numpy.ascontiguousarray(blk, dtype=numpy.int32)
+        dt = _block_dtype(A.dtype)
+        data = numpy.ascontiguousarray(A.data, dtype=dt)
+        h = _H()
+        buf = (ctypes.c_int64 * 8)()
+        fn = self._lib.kh_zbjac_create if dt == _C128 else self._lib.kh_bjac_create
+        _check(self._lib, self._with_memory(lambda: fn(
+            self._h, A.shape[0], data.size, indptr.ctypes.data_as(_c_int32_p), indices.ctypes.data_as(_c_int32_p), _dptr(data),
+            blk.size - 1, blk.ctypes.data_as(_c_int32_p), ctypes.byref(h), buf)), "kh_bjac_create")
+        return DeviceBjac(self, h, A.shape, indices.size, dt, blk), _bjac_info(buf)
+
+    def bjac_update(self, h, data):
+        """Rebuilds the inverses from the values ``data`` at the CSR positions the handle was made with
+        (``kh_bjac_update``): one upload, one launch.  Returns the refreshed ``info`` dict of :meth:`bjac_create`."""
+        if numpy.asarray(data).dtype.kind == "c" and h.dtype != _C128:
+            raise BackendError("bjac_update: complex values for a real handle")
+        data = numpy.ascontiguousarray(data, dtype=h.dtype)
+        if data.shape != (h.nnz,):
+            raise BackendError("bjac_update: %s values for a pattern of %d entries" % (data.shape, h.nnz))
+        _check(self._lib, self._lib.kh_bjac_update(h.handle, _dptr(data)), "kh_bjac_update")
+        return h.info()
+
+    def bjac_apply(self, h, X, xcol, Y, ycol, ncols=1):
+        """``Y[:, ycol:ycol+ncols] = D^{-1} X[:, xcol:xcol+ncols]`` with the handle's inverse blocks (``kh_bjac_apply``);
+        not in place.  A real handle on complex blocks, or the reverse, is refused by the library."""
+        _same_dtype("bjac_apply", X, Y)
+        _check(self._lib, self._lib.kh_bjac_apply(self._h, h.handle, X.handle, xcol, Y.handle, ycol, ncols),
+               "kh_bjac_apply")
+
+    def bjac_values(self, h):
+        """The inverse blocks as one flat array: dense row-major ``m_g x m_g`` arrays one after another in block order
+        (``kh_bjac_values``)."""
+        m = numpy.diff(h.blkptr).astype(numpy.int64)
+        out = numpy.empty(int((m * m).sum()), dtype=h.dtype)
+        _check(self._lib, self._lib.kh_bjac_values(h.handle, _dptr(out)), "kh_bjac_values")
+        return out
 
     def spai(self, A, P):
         """The sparse approximate inverse of the square SciPy CSR matrix ``A`` on the pattern of the CSR matrix ``P`` (both with

@@ -110,6 +110,8 @@ struct kh_ctx_s {
     int64_t n_spai_build = 0, spai_device_us = 0;
     // factorized sparse approximate inverse (fsai.hip): calls; device time of the last call's launch
     int64_t n_fsai_build = 0, fsai_device_us = 0;
+    // block-Jacobi (bjac.hip): build launches (create and update); columns applied; device time of the last build launch
+    int64_t n_bjac_build = 0, n_bjac_apply = 0, bjac_device_us = 0;
     // Chebyshev polynomial preconditioner (cheb.hip): steps k >= 1 as ONE launch, the SpMV with the step in its epilogue
     int cheb_fused = 1;
     void* cheb_tab = nullptr;        // device records of one application's fused steps (kernels.h: ChebArgs), cheb_tab_cap of them

@@ -1101,6 +1101,9 @@ int kh_ctx_get(kh_ctx ctx, const char* key, int64_t* value) {
     else if (!strcmp(key, "spai_device_us")) *value = ctx->spai_device_us;
     else if (!strcmp(key, "n_fsai_build")) *value = ctx->n_fsai_build;
     else if (!strcmp(key, "fsai_device_us")) *value = ctx->fsai_device_us;
+    else if (!strcmp(key, "n_bjac_build")) *value = ctx->n_bjac_build;
+    else if (!strcmp(key, "n_bjac_apply")) *value = ctx->n_bjac_apply;
+    else if (!strcmp(key, "bjac_device_us")) *value = ctx->bjac_device_us;
     else if (!strcmp(key, "cheb_fused")) *value = ctx->cheb_fused;
     else if (!strcmp(key, "n_cheb_apply")) *value = ctx->n_cheb_apply;
     else if (!strcmp(key, "n_cheb_fused")) *value = ctx->n_cheb_fused;
