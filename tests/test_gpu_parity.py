@@ -360,7 +360,9 @@ def test_shard_spmv_with_ghost_rows_on_one_gpu(hip, kind):
 @pytest.mark.parametrize("mode", ["0", "1", "2"])
 def test_banded_spmv_measurement_modes(hip, mode):
     """KRYPY_AMD_SPMV_DIA is read once per process: the non-default settings (CSR kernel, 1 and 2
-    row pairs per lane) are checked in a child process - same bits as SciPy in every mode."""
+    row pairs per lane) are checked in a child process - same bits as SciPy in every mode.  Two columns go to k_spmm_dia
+    (one row pair per lane in every mode); the ONE-column product and the residual are the launches of k_spmv_dia whose row
+    pairs per lane the mode sets (tests/test_gpu_dia.py runs the whole catalogue of banded structures the same way)."""
     import subprocess
     import sys
     code = (
@@ -369,12 +371,25 @@ def test_banded_spmv_measurement_modes(hip, mode):
         "from oracle import krylov_ref as ref\n"
         "ctx = _hip.get_context()\n"
         "for A in (ref.laplace2d(97, 53), ref.laplace3d(21).tocsr(), ref.laplace2d(1500, 700)):\n"
-        "    x = np.random.default_rng(1).standard_normal((A.shape[0], 2))\n"
+        "    n = A.shape[0]\n"
+        "    x = np.random.default_rng(1).standard_normal((n, 2))\n"
+        "    b = np.random.default_rng(2).standard_normal((n, 1))\n"
         "    Ad = ctx.csr(A)\n"
         "    assert (Ad.diagonals > 0) == (%r != '0')\n"
-        "    Y = ctx.alloc(A.shape[0], 2)\n"
-        "    ctx.apply(Ad, ctx.upload(x), 0, Y, 0, 2)\n"
+        "    X, Y = ctx.upload(x), ctx.alloc(n, 2)\n"
+        "    ctx.apply(Ad, X, 0, Y, 0, 2)\n"
         "    assert np.array_equal(Y.download(), A.dot(x))\n"
+        "    Y1 = ctx.upload(np.full((n, 1), np.nan))\n"
+        "    ctx.apply(Ad, X, 1, Y1, 0, 1)\n"
+        "    assert np.array_equal(Y1.download()[:, 0], A.dot(x[:, 1])), 'one column'\n"
+        "    R = ctx.upload(np.full((n, 1), np.nan))\n"
+        "    nrm = ctx.residual(Ad, ctx.upload(b), 0, X, 0, R, 0)\n"
+        "    want = b[:, 0] - A.dot(x[:, 0])\n"
+        "    assert np.array_equal(R.download()[:, 0], want), 'residual'\n"
+        # the square of the norm: n squares summed in any order, the root and its square - gamma_(n+2), u = 2^-53
+        "    ref2 = (want.astype(np.longdouble) ** 2).sum()\n"
+        "    assert abs(np.longdouble(nrm) ** 2 - ref2) <= (n + 3) * 2.0 ** -53 * ref2, 'residual norm'\n"
+        "    assert not Y1.padding_nonzero() and not R.padding_nonzero()\n"
         "print('ok')\n" % mode)
     env = dict(os.environ, KRYPY_AMD_SPMV_DIA=mode)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
