@@ -432,9 +432,4 @@ class ShardedCSROperator(utils.LinearOperator):
         self._ctx.apply(self._device_matrix(dtype=X.dtype), X, xcol, Y, ycol, ncols)
 
     def _dot_host(self, X):
-        X = numpy.asarray(X)
-        dt = utils._bdt(self.dtype, X.dtype)
-        Xd = self._ctx.upload(X, dtype=dt)
-        Yd = self._ctx.alloc(self.shape[0], X.shape[1], dtype=dt)
-        self._apply_dev(Xd, 0, Yd, 0, X.shape[1])
-        return numpy.ascontiguousarray(Yd.download())
+        return self._dot_via_device(X, self._ctx)

@@ -86,7 +86,7 @@ def test_oracle_pivot_cases_invert(cplx):
 def test_oracle_apply_is_the_csr_product_order(cplx):
     """The apply sum is scipy's csr_matvec order on the assembled block-diagonal matrix for real data (separate multiply and
     add, rising columns); for complex data it is that order with the product taken part by part."""
-    from krypy_amd import utils
+    from krypy_amd import precond as utils          # (_bjac_csr is private to the module the preconditioners live in)
 
     ptr = bc.cycle_ptr(40)
     A = bc.block_system(ptr, 3, cplx)

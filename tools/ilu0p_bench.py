@@ -32,7 +32,7 @@ def _counters(ctx, keys):
 
 
 def bench_setup_and_apply(ctx, nx, ny, reps, what):
-    from krypy_amd import utils
+    from krypy_amd import precond, utils
 
     A = lap2d(nx, ny)
     n = A.shape[0]
@@ -56,10 +56,10 @@ def bench_setup_and_apply(ctx, nx, ny, reps, what):
             h = M._device_handle(ctx, M.dtype)
             for _ in range(reps):
                 t0 = time.perf_counter()
-                ctx.ilu0_refactor(h, M._data)
+                ctx.ilu0_refactor(h, M._A.data)
                 call.append(time.perf_counter() - t0)
                 t0 = time.perf_counter()
-                utils._ilu0_canonical(A)
+                precond._ilu0_canonical(A)
                 canon.append(time.perf_counter() - t0)
             for _ in range(reps):
                 t0 = time.perf_counter()
