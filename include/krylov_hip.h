@@ -783,6 +783,36 @@ int kh_cheb_update(kh_ctx ctx, kh_vec AZ, int64_t azcol, kh_vec R, int64_t rcol,
 int kh_cheb_apply(kh_ctx ctx, kh_mat A, kh_mat Dinv, int m, const double* coef, kh_vec X, int64_t xcol, kh_vec Y, int64_t ycol,
                   int64_t ncols, kh_vec S);
 
+/* ---- GMRES polynomial preconditioner ------------------------------------------------------------------------------------ */
+/* Both entry points serve the Ml, Mr hooks of krypy/linsys.py: y = p(A) x with p(A) ~ A^-1 in the product form of Loe & Morgan
+ * (the roots of 1 - z p(z) are harmonic Ritz values of A, real ones as linear factors, conjugate pairs as real quadratic ones).
+ * No reference counterpart - the reference calls the user's function on host arrays.  The caller computes and orders the roots
+ * on the host and hands over a table of steps, five doubles (kind, c, a2, close, cl) each, ONE operator application per step.
+ * Per row, with s = (A in)_i, every multiply and add rounded on its own (krypy_amd/csrc/poly.hip):
+ *   kind 0 LIN   (in = prod):  y_i = y_i + (c * in_i);                      out_i = in_i - (c * s)      c = 1 / theta
+ *   kind 1 QA    (in = prod):  t = (a2 * in_i) - s;  y_i = y_i + (c * t);   out_i = t                   a2 = 2 Re theta, c = 1 / |theta|^2
+ *   kind 2 QB    (in = t):                                                  out_i = prod_i - (c * s)
+ *   kind 3 SCALE (alone):      y_i = c * x_i
+ *   the first step takes x as prod and does not read y;  close != 0 (LIN, QB): additionally y_i = y_i + (cl * out_i).
+ * Real operators on real blocks only. */
+/* Ml / Mr hooks, no reference counterpart: one composed step on single columns.  SO[:, socol] holds A in on entry and out on
+ * exit (unused by SCALE, may be NULL); P[:, pcol] is prod of a QB step (NULL otherwise); first != 0: y is only written.  in,
+ * prod, y and s/out are different columns.  Rows [n, ld) are not written.  KH_ERR_ARG: a kind outside 0 - 3; close on QA or
+ * SCALE; QB as the first step; lengths differ; columns coincide.  Counter: "n_poly_update". */
+int kh_poly_update(kh_ctx ctx, kh_vec In, int64_t incol, kh_vec P, int64_t pcol, kh_vec Y, int64_t ycol, kh_vec SO, int64_t socol,
+                   int kind, double c, double a2, double cl, int first, int close);
+/* Ml / Mr hooks, no reference counterpart.  Y[:, ycol + c] = p(A) X[:, xcol + c], c < ncols (one column after the other): all
+ * nsteps steps for a kh_mat operator in one call.  steps: nsteps x 5 doubles, row-major.  S: a caller-owned scratch block of the
+ * same length with at least 3 columns (prod ping-pongs between 0 and 1, t lives in 2); its contents on entry do not matter, and
+ * neither do Y's.  X is never written.  Every step is ONE launch - the SpMV with the step in its epilogue - when A is a real CSR
+ * handle without halo, the context has no communicator, and kh_ctx_set "poly_fused" (default 1) is on; otherwise kh_apply + the
+ * update kernel: the same bits.  KH_ERR_ARG: nsteps < 1; A diagonal, complex or not square; lengths differ; S has fewer than 3
+ * columns; X and Y overlap; S is X or Y; a kind outside 0 - 3; close on a QA step; a SCALE step that does not stand alone; a QB
+ * step not preceded by QA.
+ * Counters (kh_ctx_get): "n_poly_apply" columns applied, "n_poly_fused" fused launches, "n_poly_update" update launches. */
+int kh_poly_apply(kh_ctx ctx, kh_mat A, int nsteps, const double* steps, kh_vec X, int64_t xcol, kh_vec Y, int64_t ycol,
+                  int64_t ncols, kh_vec S);
+
 /* ---- measurement ----------------------------------------------------------------------- */
 /* bench.py's roofline numbers: average duration (ms) of `reps` back-to-back launches of one hot
  * kernel, HIP events on the context's stream.  which: 0 Gram-Schmidt link (axpy+dot),

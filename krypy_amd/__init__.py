@@ -9,8 +9,8 @@ HIP kernels for gfx950 through a ctypes C-ABI (``include/krylov_hip.h``).
 There is no CPU fallback: without ``libkrylov_hip.so`` and an MI355X every solve raises
 ``krypy_amd.utils.BackendError``.
 """
-from . import deflation, linsys, recycling, utils
+from . import deflation, linsys, polyprecond, recycling, utils
 from .__about__ import __version__
 from ._convenience import bicgstab, cg, gmres, idrs, minres
 
-__all__ = ["linsys", "deflation", "recycling", "utils", "cg", "minres", "gmres", "bicgstab", "idrs", "__version__"]
+__all__ = ["linsys", "deflation", "recycling", "utils", "polyprecond", "cg", "minres", "gmres", "bicgstab", "idrs", "__version__"]

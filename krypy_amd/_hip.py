@@ -149,6 +149,9 @@ _SIGNATURES = {
     # Chebyshev polynomial preconditioner (csrc/cheb.hip)
     "kh_cheb_update": [_H, _H, _I64, _H, _I64, _H, _H, _I64, _H, _I64, _H, _I64, _D, _D, _INT],
     "kh_cheb_apply": [_H, _H, _H, _INT, _c_double_p, _H, _I64, _H, _I64, _I64, _H],
+    # GMRES polynomial preconditioner (csrc/poly.hip)
+    "kh_poly_update": [_H, _H, _I64, _H, _I64, _H, _I64, _H, _I64, _INT, _D, _D, _D, _INT, _INT],
+    "kh_poly_apply": [_H, _H, _INT, _c_double_p, _H, _I64, _H, _I64, _I64, _H],
     "kh_residual": [_H, _H, _H, _I64, _H, _I64, _H, _I64, _c_double_p],
     "kh_gmres_cycle": [_H, _H, _H, _H, _H, _H, _I64, _I64, _I64, _INT, _INT, _c_int64_p, _D, _D, _c_double_p, _I64,
                        _c_double_p, _I64, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_int64_p,
@@ -1027,6 +1030,30 @@ class Context(object):
         _check(self._lib, self._lib.kh_cheb_apply(
             self._h, A.handle, None if Dinv is None else Dinv.handle, coef.shape[0], _dptr(coef), X.handle, xcol, Y.handle,
             ycol, ncols, S.handle), "kh_cheb_apply")
+
+    def poly_update(self, In, incol, P, pcol, Y, ycol, SO, socol, kind, c, a2=0.0, cl=0.0, first=False, close=False):
+        """One composed step of the GMRES polynomial preconditioner on single columns (``kh_poly_update``): ``SO[:, socol]``
+        holds ``A in`` on entry and ``out`` on exit (None for a SCALE step), ``P[:, pcol]`` is ``prod`` of a QB step (None
+        otherwise).  Real blocks only."""
+        blocks = [B for B in (In, Y, SO, P) if B is not None]
+        if _same_dtype("poly_update", *blocks):
+            raise BackendError("poly_update: real operator on %s blocks" % (In.dtype,))
+        h = lambda B: None if B is None else B.handle   # noqa: E731
+        _check(self._lib, self._lib.kh_poly_update(
+            self._h, In.handle, incol, h(P), pcol, Y.handle, ycol, h(SO), socol, int(kind), float(c), float(a2), float(cl),
+            1 if first else 0, 1 if close else 0), "kh_poly_update")
+
+    def poly_apply(self, A, steps, X, xcol, Y, ycol, ncols, S):
+        """``Y[:, ycol:ycol+ncols] = p(A) X[:, xcol:xcol+ncols]``: all steps of the GMRES polynomial preconditioner in one call
+        (``kh_poly_apply``).  ``steps``: the ``(nsteps, 5)`` table of ``(kind, c, a2, close, cl)``; ``S``: scratch block with 3
+        columns; ``X`` and ``Y`` are different columns.  Real operators on real blocks only."""
+        if _same_dtype("poly_apply", X, Y, S) or A.dtype == _C128:
+            raise BackendError("poly_apply: %s operator on %s blocks (real operators on real blocks only)" % (A.dtype, X.dtype))
+        steps = numpy.ascontiguousarray(steps, dtype=numpy.float64)
+        if steps.ndim != 2 or steps.shape[1] != 5:
+            raise BackendError("poly_apply: an (nsteps, 5) table of steps expected, got shape %s" % (steps.shape,))
+        _check(self._lib, self._lib.kh_poly_apply(
+            self._h, A.handle, steps.shape[0], _dptr(steps), X.handle, xcol, Y.handle, ycol, ncols, S.handle), "kh_poly_apply")
 
     # ---- numerics (each is one C entry point; complex blocks go to the kh_z* twin) ----
     def apply(self, A, X, xcol, Y, ycol, ncols=1):

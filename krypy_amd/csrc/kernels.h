@@ -444,7 +444,9 @@ __global__ __launch_bounds__(BS) void k_cg_update(int64_t n, double alpha,
 //            EPI_CHEB one step k >= 1 of the Chebyshev iteration (cheb.hip), row-local behind the row sum s = (A z)_i:
 //                     t = r_i - s; [t = t * dinv_i;] d_i = (a * d_i) + (b * t); y_i = z_i + d_i   (x = z, every operation
 //                     rounded on its own).  No reduction (part_out is not touched), no halo.
-enum { EPI_NONE = 0, EPI_DOT = 1, EPI_RES = 2, EPI_CHEB = 3 };
+//            EPI_POLY one step of the GMRES polynomial preconditioner (poly.hip), row-local behind the row sum s = (A in)_i
+//                     (x = in, y = out; the formulas stand at PolyArgs).  No reduction, no halo.
+enum { EPI_NONE = 0, EPI_DOT = 1, EPI_RES = 2, EPI_CHEB = 3, EPI_POLY = 4 };
 
 // What EPI_CHEB needs beyond the SpMV's own arguments (x = z_in, y = z_out).  The record lives in DEVICE memory and the kernel
 // finds it behind `aux` (one uniform 40-byte load): the argument lists of k_spmv_stream / k_spmv_dia - and with them every
@@ -547,6 +549,109 @@ static __global__ __launch_bounds__(BS) void k_cheb_first(int64_t n, double* __r
 // ... further records (more than KH_CHEB_PLAN + 1 steps)
 static __global__ __launch_bounds__(BS) void k_cheb_plan(ChebArgs* __restrict__ tab, ChebPlan p) { cheb_plan_write(tab, p); }
 
+// ------------------------------------------------------------------------------------------
+// GMRES polynomial preconditioner (poly.hip): y = p(A) x as a product of linear and quadratic factors, one operator
+// application per step.  One step, per row, with s = (A in)_i and every multiply and add rounded on its own:
+//   LIN   (in = prod):  y_i = y_i + (c * in_i);                         out_i = in_i - (c * s)
+//   QA    (in = prod):  t = (a2 * in_i) - s;   y_i = y_i + (c * t);     out_i = t
+//   QB    (in = t):                                                     out_i = prod_i - (c * s)
+//   SCALE (no product): y_i = c * in_i
+//   first:  y_i = (c * ...) without reading y;   close:  additionally y_i = y_i + (cl * out_i)
+// What EPI_POLY needs beyond the SpMV's own arguments (x = in, y = out): a record in DEVICE memory behind `aux`, as ChebArgs.
+// ------------------------------------------------------------------------------------------
+enum { POLY_LIN = 0, POLY_QA = 1, POLY_QB = 2, POLY_SCALE = 3 };
+enum { POLY_FIRST = 1, POLY_CLOSE = 2 };
+struct PolyArgs {
+    double* y;             // the result, accumulated over the steps
+    const double* prod;    // QB: the running product (another column than in and out)
+    double c, a2, cl;
+    int kind, flags;
+};
+
+__device__ __forceinline__ PolyArgs poly_args(const double* aux) { return *reinterpret_cast<const PolyArgs*>(aux); }
+
+// the arithmetic of one row: returns out_i; yv is y_i on entry (unused when first) and on exit, *ywrite whether it changed
+__device__ __forceinline__ double poly_step(int kind, int flags, double c, double a2, double cl, double in, double pv, double s,
+                                            double& yv, bool& ywrite) {
+    const bool first = (flags & POLY_FIRST) != 0;
+    double out;
+    ywrite = true;
+    if (kind == POLY_LIN) {
+        const double u = c * in;
+        yv = first ? u : yv + u;
+        out = in - (c * s);
+    } else if (kind == POLY_QA) {
+        const double t = (a2 * in) - s;
+        const double u = c * t;
+        yv = first ? u : yv + u;
+        out = t;
+    } else {
+        out = pv - (c * s);
+        ywrite = false;
+    }
+    if (flags & POLY_CLOSE) {
+        yv = yv + (cl * out);
+        ywrite = true;
+    }
+    return out;
+}
+
+// one row of the step: returns out_i, stores y_i (read by the next launch, not by this one: non-temporal)
+__device__ __forceinline__ double poly_row(const PolyArgs& pa, int64_t i, double in, double s) {
+    const bool ready = pa.kind == POLY_QB ? (pa.flags & POLY_CLOSE) != 0 : (pa.flags & POLY_FIRST) == 0;
+    double yv = ready ? pa.y[i] : 0.0;
+    const double pv = pa.kind == POLY_QB ? pa.prod[i] : 0.0;
+    bool yw;
+    const double out = poly_step(pa.kind, pa.flags, pa.c, pa.a2, pa.cl, in, pv, s, yv, yw);
+    if (yw) st_nt(pa.y + i, yv);
+    return out;
+}
+
+// ... and an aligned pair of neighbouring rows with 16-byte accesses
+__device__ __forceinline__ double2 poly_row2(const PolyArgs& pa, int64_t i, double2 in, double2 s) {
+    const bool ready = pa.kind == POLY_QB ? (pa.flags & POLY_CLOSE) != 0 : (pa.flags & POLY_FIRST) == 0;
+    double2 yv = make_double2(0.0, 0.0), pv = make_double2(0.0, 0.0);
+    if (ready) yv = ld_nt2(reinterpret_cast<const double2*>(pa.y + i));
+    if (pa.kind == POLY_QB) pv = ld_nt2(reinterpret_cast<const double2*>(pa.prod + i));
+    bool yw;
+    double2 out;
+    out.x = poly_step(pa.kind, pa.flags, pa.c, pa.a2, pa.cl, in.x, pv.x, s.x, yv.x, yw);
+    out.y = poly_step(pa.kind, pa.flags, pa.c, pa.a2, pa.cl, in.y, pv.y, s.y, yv.y, yw);
+    if (yw) st_nt2(reinterpret_cast<double2*>(pa.y + i), yv);
+    return out;
+}
+
+// The composed step: so[i] holds s = (A in)_i on entry and out_i on exit (row-local, in place); SCALE reads no s.
+static __global__ __launch_bounds__(BS) void k_poly_update(int64_t n, const double* __restrict__ in,
+                                                    const double* __restrict__ prod, double* __restrict__ y, double* so,
+                                                    double c, double a2, double cl, int kind, int flags) {
+    const int64_t stride = (int64_t)gridDim.x * BS;
+    for (int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x; i < n; i += stride) {
+        if (kind == POLY_SCALE) {
+            st_nt(y + i, c * in[i]);
+            continue;
+        }
+        const bool ready = kind == POLY_QB ? (flags & POLY_CLOSE) != 0 : (flags & POLY_FIRST) == 0;
+        double yv = ready ? y[i] : 0.0;
+        const double pv = kind == POLY_QB ? prod[i] : 0.0;
+        bool yw;
+        const double out = poly_step(kind, flags, c, a2, cl, in[i], pv, so[i], yv, yw);
+        if (yw) st_nt(y + i, yv);
+        st_nt(so + i, out);
+    }
+}
+
+// The records of the fused steps, written by ONE workgroup: tab[k0 + t] = rec[t], t < count.
+constexpr int KH_POLY_PLAN = 16;      // records one launch writes
+struct PolyPlan {
+    PolyArgs rec[KH_POLY_PLAN];
+    int k0, count;
+};
+
+static __global__ __launch_bounds__(BS) void k_poly_plan(PolyArgs* __restrict__ tab, PolyPlan p) {
+    if (blockIdx.x == 0 && (int)threadIdx.x < p.count) tab[p.k0 + threadIdx.x] = p.rec[threadIdx.x];
+}
+
 __device__ __forceinline__ int xcd_remap(int b, int nblk) {
     const int q = nblk >> 3, r = nblk & 7;
     const int xcd = b & 7, idx = b >> 3;
@@ -644,6 +749,7 @@ __global__ __launch_bounds__(BS) void k_spmv_stream(const int32_t* __restrict__ 
                 acc = fma(s, s, acc);
             }
             if constexpr (EPI == EPI_CHEB) s = cheb_row(cheb_args(aux), r, x[r], s);
+            if constexpr (EPI == EPI_POLY) s = poly_row(poly_args(aux), r, x[r], s);
             st_nt(y + r, s);
             if (EPI == EPI_DOT) acc = fma(aux[r], s, acc);
         }
@@ -662,11 +768,12 @@ __global__ __launch_bounds__(BS) void k_spmv_stream(const int32_t* __restrict__ 
                 acc = s * s;
             }
             if constexpr (EPI == EPI_CHEB) s = cheb_row(cheb_args(aux), r0, x[r0], s);
+            if constexpr (EPI == EPI_POLY) s = poly_row(poly_args(aux), r0, x[r0], s);
             y[r0] = s;
             if (EPI == EPI_DOT) acc = aux[r0] * s;
         }
     }
-    if (EPI != EPI_NONE && EPI != EPI_CHEB) {
+    if (EPI != EPI_NONE && EPI != EPI_CHEB && EPI != EPI_POLY) {
         const double r = block_sum(acc, sm);
         if (threadIdx.x == 0) part_out[part_off + blockIdx.x] = r;
     }
@@ -860,6 +967,7 @@ __global__ __launch_bounds__(BS) void k_spmv_dia(DiaOffs o, const double* __rest
                                                  int blk_lo = 0x7fffffff, int blk_skip = 0, int part_off = 0,
                                                  XhArgs xh = XhArgs()) {
     static_assert(EPI != EPI_CHEB || (!HALO && !XH), "EPI_CHEB has no halo form");
+    static_assert(EPI != EPI_POLY || (!HALO && !XH), "EPI_POLY has no halo form");
     __shared__ double sm[8];
     int lb, pslot = blockIdx.x;
     if constexpr (XH) {
@@ -1009,6 +1117,19 @@ __global__ __launch_bounds__(BS) void k_spmv_dia(DiaOffs o, const double* __rest
                     v1 = cheb_row(ch, r + 1, x[r + 1], v1);
                 }
             }
+            if constexpr (EPI == EPI_POLY) {
+                const PolyArgs pa = poly_args(aux);
+                // y, prod and x allow 16-byte accesses to a row pair (out does: the launcher)
+                const bool pal = xal && ((reinterpret_cast<uintptr_t>(pa.y) | reinterpret_cast<uintptr_t>(pa.prod)) & 15) == 0;
+                if (pal) {
+                    const double2 o2 = poly_row2(pa, r, *reinterpret_cast<const double2*>(x + r), make_double2(v0, v1));
+                    v0 = o2.x;
+                    v1 = o2.y;
+                } else {
+                    v0 = poly_row(pa, r, x[r], v0);
+                    v1 = poly_row(pa, r + 1, x[r + 1], v1);
+                }
+            }
             st_nt2(reinterpret_cast<double2*>(y + r), make_double2(v0, v1));
         } else if (r < n) {
             if (EPI == EPI_RES) {
@@ -1017,10 +1138,11 @@ __global__ __launch_bounds__(BS) void k_spmv_dia(DiaOffs o, const double* __rest
             }
             if (EPI == EPI_DOT) acc = fma(aux[r], v0, acc);
             if constexpr (EPI == EPI_CHEB) v0 = cheb_row(cheb_args(aux), r, x[r], v0);
+            if constexpr (EPI == EPI_POLY) v0 = poly_row(poly_args(aux), r, x[r], v0);
             y[r] = v0;
         }
     }
-    if (EPI != EPI_NONE && EPI != EPI_CHEB) {
+    if (EPI != EPI_NONE && EPI != EPI_CHEB && EPI != EPI_POLY) {
         const double r = block_sum(acc, sm);
         if (threadIdx.x == 0) part_out[part_off + pslot] = r;
     }

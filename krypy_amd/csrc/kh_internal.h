@@ -117,6 +117,11 @@ struct kh_ctx_s {
     void* cheb_tab = nullptr;        // device records of one application's fused steps (kernels.h: ChebArgs), cheb_tab_cap of them
     int64_t cheb_tab_cap = 0;
     int64_t n_cheb_apply = 0, n_cheb_fused = 0, n_cheb_update = 0;   // columns applied; fused launches; launches of k_cheb_update
+    // GMRES polynomial preconditioner (poly.hip): every step as ONE launch, the SpMV with the step in its epilogue
+    int poly_fused = 1;
+    void* poly_tab = nullptr;        // device records of one application's fused steps (kernels.h: PolyArgs), poly_tab_cap of them
+    int64_t poly_tab_cap = 0;
+    int64_t n_poly_apply = 0, n_poly_fused = 0, n_poly_update = 0;   // columns applied; fused launches; launches of k_poly_update
     int64_t n_spmm = 0;     // panel applications of a CSR operator that streamed the matrix once
     int chain_spmv = 1;     // banded operators: w = A v_k in the chain kernel's prologue (KRYPY_AMD_CHAIN_SPMV)
     int chain_pf = 1;       // ... and keep HBM busy through the update phase (k_mgs_chain_pf; KRYPY_AMD_CHAIN_PF)

@@ -861,6 +861,7 @@ int kh_ctx_destroy(kh_ctx ctx) {
     }
     (void)hipFree(ctx->cgs_part);
     (void)hipFree(ctx->cheb_tab);
+    (void)hipFree(ctx->poly_tab);
     (void)hipFree(ctx->chain_gran);
     (void)hipFree(ctx->chain_xcc);
     (void)hipFree(ctx->onex_ticket);
@@ -1003,6 +1004,7 @@ int kh_ctx_set(kh_ctx ctx, const char* key, int64_t value) {
         ctx->tri_narrow_rows = value;
     }
     else if (!strcmp(key, "cheb_fused")) ctx->cheb_fused = value ? 1 : 0;     // kh_cheb_apply: the fused epilogue where it applies
+    else if (!strcmp(key, "poly_fused")) ctx->poly_fused = value ? 1 : 0;     // kh_poly_apply: likewise
     else if (!strcmp(key, "chain_epoch")) ctx->chain_epoch = (unsigned)value;      // tests: bring the epoch counter of the grid-wide sums near its wrap
     else if (!strcmp(key, "chain_debug")) ctx->chain_debug = (int)value;    // measurement: phases switched off (garbage results)
     else return fail(KH_ERR_ARG, "kh_ctx_set: unknown key '%s'", key);
@@ -1108,6 +1110,10 @@ int kh_ctx_get(kh_ctx ctx, const char* key, int64_t* value) {
     else if (!strcmp(key, "n_cheb_apply")) *value = ctx->n_cheb_apply;
     else if (!strcmp(key, "n_cheb_fused")) *value = ctx->n_cheb_fused;
     else if (!strcmp(key, "n_cheb_update")) *value = ctx->n_cheb_update;
+    else if (!strcmp(key, "poly_fused")) *value = ctx->poly_fused;
+    else if (!strcmp(key, "n_poly_apply")) *value = ctx->n_poly_apply;
+    else if (!strcmp(key, "n_poly_fused")) *value = ctx->n_poly_fused;
+    else if (!strcmp(key, "n_poly_update")) *value = ctx->n_poly_update;
     else if (!strcmp(key, "chain_epoch")) *value = ctx->chain_epoch;
     else if (!strcmp(key, "n_epoch_wraps")) *value = ctx->n_epoch_wraps;
     else return fail(KH_ERR_ARG, "kh_ctx_get: unknown key '%s'", key);

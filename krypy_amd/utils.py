@@ -2050,3 +2050,6 @@ from .precond import (BlockJacobiPreconditioner, ChebyshevOperator, Ilu0Factors,
                       TriangularSolveOperator, block_jacobi, block_jacobi_operator, chebyshev_coefficients,
                       chebyshev_operator, fsai, fsai_operator, ilu0, ilu0_operator, ilu0_preconditioner, ilu_operator,
                       spai, spai_operator)
+# ... and so does polyprecond.py (not in __all__: reachable as utils.NAME)
+from .polyprecond import (GmresPolynomialOperator, gmres_polynomial_operator, gmres_polynomial_roots,  # noqa: E402, F401
+                          gmres_polynomial_steps)
